@@ -1,22 +1,33 @@
 #!/usr/bin/env python3
 """Benchmark of the RBM CD-1 hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it sets up, runs W untimed warm-up steps, times exactly K
+steps, writes its outputs if --dump-outputs is given, and prints the result line.  Everything else this file measures -- the
+further blocks of the block protocol, the variants, the per-kernel and whole-path timings, the roofline and the CPU baseline,
+all described below -- runs only with --full, after the K timed steps of the headline, and adds its keys to the same line.
+
+--dump-outputs DIR: what a caller of the timed path holds after the last of the K timed steps -- the updated parameters, as
+DIR/W.npy [784, 1024], DIR/b_h.npy [1024] and DIR/b_v.npy [784], float32 (3.2 MB), read back before anything else runs.  The
+weights, the data and every draw are seeded, so the same arguments give the same inputs in every run and two builds can be
+compared output for output.
 
 Metric (BASELINE.json): CD-1 Gibbs-steps/sec on a 784-visible x 1024-hidden RBM at batch 4096, fp32 storage /
 accumulation / results, synthetic binary data resident in HBM.  One "step" (the unit of `value`) = one full CD-1
 parameter update over 4096 rows: h_pos sample, v_neg sample, h_neg probabilities, dW / db_h / db_v applied
 (update_mode "fused").  --compute picks how the matrix products run: "x3" (default: fp32 values carried as exact
 bf16 triples on the bf16 matrix cores -- held to the fp32 oracle and the fp32 tolerances by the tests) or "fp32"
-(fp32 MFMA); rank 0 times BOTH after the timed region and reports them under `paths`, next to the real-valued-data
-and Gaussian-mode (the reference's default) variants.
+(fp32 MFMA); with --full rank 0 times BOTH after the timed region and reports them under `paths`, next to the
+real-valued-data and Gaussian-mode (the reference's default) variants.
 
-Timing protocol: W untimed warm-up steps, then R blocks of exactly K steps, each bracketed by a barrier +
-torch.cuda.synchronize() on both sides (R = max(5, ceil(2000 / K)): at least 2 000 timed steps, ~0.2 s of GPU work, so
-that the median block is past the clock ramp of a GPU that was idle when the process started); the block time is the MAX
-over ranks.  `value` = N * K / median(block times); `value_first_block` is the first block alone (a cold GPU: the
-step time falls ~15 % over the first ~20 ms while the clocks ramp); `value_steady` is the median of R more blocks
-after 256 further untimed steps.  All three are on the line, labelled in config.timing.
+Timing protocol: the set-up ends with 512 steps whose updates are discarded (the parameters are put back afterwards: a GPU that
+was idle when the process started runs its first ~20 ms at lower clocks, the step time falling ~15 % meanwhile, and K may be
+small), then W untimed warm-up steps, then ONE block of exactly K steps, bracketed by a barrier + torch.cuda.synchronize() on
+both sides; the block time is the MAX over ranks.  `value` = N * K / that time, `ms_per_step` = that time / K.
+With --full, R - 1 more blocks of K steps follow (R = max(5, ceil(2000 / K)): at least 2 000 timed steps):
+`value_block_median` = N * K / median(all R block times), `value_first_block` is the first block alone (= `value`), and
+`value_steady` is the median of R more blocks after 256 further untimed steps.  All are on the line, labelled in config.timing.
 
 With N > 1 (one process per GPU, torch.distributed.run) every rank processes its own 4096 rows per step (weak scaling:
 global batch 4096 N, config 3 at N = 8) through kurbm_cd_step_x3_dp: the packed [dW|db_h|db_v] sums (3.2 MB) are all-reduced
@@ -26,7 +37,7 @@ communicator itself.  `rccl_ranks` is ncclCommCount's answer.  UNVERIFIED ON HAR
 available to this build, so the N > 1 path has run only at world size 1 (BENCH_FORCE_DP=1), on CPU doubles at world size 2
 (tests/test_dp_gloo.py), and in tests/test_two_gpus.py nowhere yet.
 
-The line also carries `roofline` (dominant kernel, HIP-event timed on the launch stream, and the whole step) and
+With --full the line also carries `roofline` (dominant kernel, HIP-event timed on the launch stream, and the whole step) and
 `cpu_baseline` (oracle/cpu_baseline.py: the same op sequence on torch-CPU over all host cores; rank 0, N = 1 only).
 """
 import argparse
@@ -50,12 +61,20 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the parameters as they stand after the last timed step to DIR/W.npy, DIR/b_h.npy, DIR/b_v.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the rest of the block protocol, the variants, the per-kernel and whole-path "
+                         "timings, the roofline and the CPU baseline, and report them on the same line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
     ap.add_argument("--no-variants", action="store_true",
-                    help="skip paths.* beyond x3 / fp32 (real-valued data, Gaussian mode): they launch the SAME kernels with more "
+                    help="with --full: skip paths.* beyond x3 / fp32 (real-valued data, Gaussian mode): they launch the SAME kernels with more "
                          "segments, which would blur a rocprofv3 --stats average of the config-2 launches (tools/profile_round.sh)")
     ap.add_argument("--compute", choices=("x3", "fp32"), default=os.environ.get("BENCH_COMPUTE", "x3"))
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def self_launch(args):
@@ -96,6 +115,7 @@ FLOP_STEP = 3 * FLOP_HALF + FLOP_OUTER             # 10 B V H, the algorithmic w
 # 6+3+3 and 3+3; Gaussian visibles on real-valued data 6+3+(3+2+1) and 3+(3+2+1)
 X3_UNITS = {"binary": 13, "real": 18, "gaussian_real": 24}
 SETTLE_STEPS = 256
+RAMP_STEPS = 512      # ~50 ms of steps before the warm-up: the clocks of a GPU that was idle are up after ~20 ms
 
 
 def event_time_ms(fn, iters, warm=3):
@@ -110,6 +130,14 @@ def event_time_ms(fn, iters, warm=3):
     t1.record()
     torch.cuda.synchronize()
     return t0.elapsed_time(t1) / iters
+
+
+def dump_outputs(eng, out_dir):
+    """--dump-outputs: the parameters as the last timed step left them -- what the caller of a CD-1 update holds afterwards --
+    as float32 W.npy [n_vis, n_hid], b_h.npy [n_hid], b_v.npy [n_vis] (every rank of a data-parallel run holds the same ones)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in zip(("W", "b_h", "b_v"), eng.get_weights()):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def choose_exchange(eng, V, device, rank, world, planes, lr, seed, compute):
@@ -274,27 +302,41 @@ def main():
             dt = float(t.item())
         return dt
 
+    # the clocks come up on steps that leave no trace: the parameters are put back, the step counter does not move
+    keep = [eng.W.t.clone(), eng.b_h.clone(), eng.b_v.clone()]
+    for i in range(RAMP_STEPS):
+        step(i)
+    for dst, src in zip((eng.W.t, eng.b_h, eng.b_v), keep):
+        dst.copy_(src)
+    eng._weights_written()      # (the bf16 pieces of W are made again from the fp32 W by the first step)
+    del keep
+
     for _ in range(args.warmup):
         step(counter[0])
         counter[0] += 1
-    repeats = max(5, math.ceil(2000 / max(args.steps, 1)))
-    blocks = [timed_block(args.steps) for _ in range(repeats)]
-    for _ in range(SETTLE_STEPS):
-        step(counter[0])
-        counter[0] += 1
-    steady = [timed_block(args.steps) for _ in range(repeats)]
+    blocks = [timed_block(args.steps)]       # the headline: exactly --steps timed steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)
+    repeats, steady = 1, []
+    if args.full:
+        repeats = max(5, math.ceil(2000 / args.steps))
+        blocks += [timed_block(args.steps) for _ in range(repeats - 1)]
+        for _ in range(SETTLE_STEPS):
+            step(counter[0])
+            counter[0] += 1
+        steady = [timed_block(args.steps) for _ in range(repeats)]
     assert bool(torch.isfinite(eng.W.t).all().item()), "weights diverged"
     eng.check_status()   # (a device-side wait that timed out -- the peer exchange -- would have skipped updates: not a measurement)
     fence()          # every rank is past its last data-parallel step; from here on only rank 0 touches its GPU
 
-    # ---- the honest variants, under the SAME block protocol as `value` (single GPU, x3) -------------------------------------
+    # ---- --full: the honest variants, under the SAME block protocol as `value_block_median` (single GPU, x3) ----------------
     # value_convert_per_step: no resident planes -- every step converts its own 4096 rows, as the FIRST epoch of a fit() does
     #   for every window (the reference's example conf is `epochs: 1`: rbm_softmax_mnist_conf.json:14);
     # value_reference_default: what `RBM(hps, n).fit(V)` is in the reference -- the constructor's default Gaussian-visible mode
     #   (rbm.py:22) on grey-level data (rbm_softmax_mnist.py:103) with the default verbose = 1, i.e. the update AND the score pass
     #   (rbm.py:225-234) every step; planes resident, the score left on the device as fit() leaves it.
     variants = {}
-    if world == 1 and args.compute == "x3" and not args.no_variants:
+    if args.full and world == 1 and args.compute == "x3" and not args.no_variants:
         from keras_unsupervised_amd.ebm.engine import CHAIN_SCORE
 
         def protocol(step_fn):
@@ -330,7 +372,7 @@ def main():
         variants["value_reference_default"] = protocol(ref_default)
         variants["value_reference_default_quiet"] = protocol(lambda i: ref_default(i, score=False))
         variants["value_grey_level_bernoulli"] = protocol(lambda i: ref_default(i, score=False, mode=0))
-        variants["note"] = ("same block protocol as `value` (W = %d warm-up steps, %d blocks of %d steps, median): value_convert_per_step = 0/1 data, "
+        variants["note"] = ("same block protocol as `value_block_median` (W = %d warm-up steps, %d blocks of %d steps, median): value_convert_per_step = 0/1 data, "
                             "no resident planes (the epochs: 1 case); value_reference_default = Gaussian-visible mode (rbm.py:22) on grey-level "
                             "data with the score pass of fit(verbose=1) (rbm.py:225-234) in every step; _quiet = the same without the score; "
                             "value_grey_level_bernoulli = Bernoulli mode on the same data, no score" % (args.warmup, repeats, args.steps))
@@ -339,11 +381,12 @@ def main():
         fence()
 
     out = None
-    if rank == 0:
-        elapsed = statistics.median(blocks)
-        ms_per_step = elapsed / args.steps * 1e3
-        value = world * args.steps / elapsed
-        rate = lambda dt: world * args.steps / dt
+    elapsed = blocks[0]
+    ms_per_step = elapsed / args.steps * 1e3
+    value = world * args.steps / elapsed
+    rate = lambda dt: world * args.steps / dt
+    paths = roofline = None
+    if rank == 0 and args.full:
         import ctypes as C
         from keras_unsupervised_amd import _lib
         # ---- per-kernel durations (HIP events on the launch stream), each launched alone --------------------------
@@ -475,45 +518,53 @@ def main():
             dom = max(kern, key=lambda k: kern[k]["ms"])
             roofline = {"bound": "mfma", "kernel": dom, "achieved": kern[dom]["tflops"], "peak": PEAK_F32_MFMA_TFLOPS,
                         "unit": "TFLOP/s", "frac": kern[dom]["frac"],
-                        "traffic": traffic_all.get(dom_pmc, {}).get("hbm_bytes_per_launch"),
+                        "traffic": traffic_all.get(dom, {}).get("hbm_bytes_per_launch"),
                         "traffic_source": "%s (rocprofv3 --pmc passes of an earlier run; not measured in this run)" % traffic_file,
                         "step": {"algorithmic_tflops": FLOP_STEP / (ms_per_step * 1e-3) / 1e12 * world,
                                  "frac": FLOP_STEP / (ms_per_step * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS},
                         "kernels": kern, "kernels_x3_path": kern_x3}
+    if rank == 0:
         dtype = ("f32 (storage, accumulation, results); products as exact bf16 triples on the bf16 MFMA (x3), the 0/1 x 0/1 "
                  "product of the positive statistics on the fp8 MFMA (exact)" if args.compute == "x3" else "f32")
+        timing = {"blocks": repeats, "steps_per_block": args.steps,
+                  "value": "N x K / time of the one block of K = %d timed steps; before it %d steps whose updates are discarded "
+                           "(clock ramp) and W = %d untimed warm-up steps" % (args.steps, RAMP_STEPS, args.warmup),
+                  "block_ms": [b * 1e3 for b in blocks]}
         out = {
             "metric": "cd1_gibbs_steps_per_sec", "value": value,
             "unit": "steps/s (1 step = CD-1 update over 4096 rows, 784x1024 fp32)",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": "synthetic",
-            "value_first_block": rate(blocks[0]), "value_steady": rate(statistics.median(steady)),
+            "full": args.full, "outputs": args.dump_outputs,
             "rccl_ranks": rccl_ranks,
-            "value_convert_per_step": variants.get("value_convert_per_step", {}).get("value"),
-            "value_reference_default": variants.get("value_reference_default", {}).get("value"),
-            "variants": variants or None,
             "config": {"workload": "rbm_784x1024_cd1_batch4096_fp32 (BASELINE.json configs[1]%s)" % ("" if world == 1 else "; configs[2] shape: 4096 rows per GPU"),
                        "n_vis": N_VIS, "n_hid": N_HID, "batch_per_gpu": BATCH, "global_batch": BATCH * world,
                        "cd_k": 1, "update_mode": "fused", "lr": "1e-3/4096", "parallelism": "dp%d" % world,
                        "compute": args.compute, "flop_per_step": FLOP_STEP,
                        "data_planes": None if planes is None else "resident: bf16 planes of the 16 batch windows made once before the warm-up "
-                                      "(%.0f MB), as RBM.fit does once per call; paths.x3_convert_per_step converts the batch in every step" % (planes.buf.numel() / 1e6),
+                                      "(%.0f MB), as RBM.fit does once per call; paths.x3_convert_per_step (--full) converts the batch in every step" % (planes.buf.numel() / 1e6),
                        "data_parallel_step": None if comm is None else (
                            "kurbm_cd_step_x3_peer (two-shot all-reduce over hipIpc peer pointers, the apply fused into its second shot)"
                            if hasattr(comm, "capacity") else
                            "kurbm_cd_step_x3_dp (RCCL all-reduce inside libkurbm.so; row ranges: KURBM_DP_CHUNKS, default one)"),
                        "exchange": exchange_note,
-                       "timing": {"blocks": repeats, "steps_per_block": args.steps,
-                                  "value": "N x K / median block time; W = %d untimed warm-up steps before the first block" % args.warmup,
-                                  "value_first_block": "first block alone (cold clocks)",
-                                  "value_steady": "median of %d more blocks after %d further untimed steps" % (repeats, SETTLE_STEPS),
-                                  "block_ms": [b * 1e3 for b in blocks], "steady_block_ms": [b * 1e3 for b in steady]}},
-            "paths": paths,
-            "roofline": roofline,
+                       "timing": timing},
         }
-        if world == 1 and not args.no_cpu_baseline:
-            from oracle import cpu_baseline
-            out["cpu_baseline"] = cpu_baseline.run(N_VIS, N_HID, BATCH)
+        if args.full:
+            timing.update({"value_block_median": "N x K / median time of the %d blocks of K steps, the block of `value` first" % repeats,
+                           "value_first_block": "first block alone (= value)",
+                           "value_steady": "median of %d more blocks after %d further untimed steps" % (repeats, SETTLE_STEPS),
+                           "steady_block_ms": [b * 1e3 for b in steady]})
+            out.update({"value_block_median": rate(statistics.median(blocks)),
+                        "value_first_block": rate(blocks[0]), "value_steady": rate(statistics.median(steady)),
+                        "value_convert_per_step": variants.get("value_convert_per_step", {}).get("value"),
+                        "value_reference_default": variants.get("value_reference_default", {}).get("value"),
+                        "variants": variants or None,
+                        "paths": paths,
+                        "roofline": roofline})
+            if world == 1 and not args.no_cpu_baseline:
+                from oracle import cpu_baseline
+                out["cpu_baseline"] = cpu_baseline.run(N_VIS, N_HID, BATCH)
     if dist.is_initialized():
         dist.barrier()   # (gloo: the other ranks wait here, on the host, while rank 0 measures)
     if comm is not None:

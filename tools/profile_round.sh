@@ -1,7 +1,7 @@
 # The measurement record of the kernels that ship, one script for every round:
 #     bash tools/profile_round.sh TAG [part ...]          -> gpurun_out/TAG/   (copy what is to be judged into profiles/ as TAG_*)
 # parts (default: all):
-#   bench     bench.py with its defaults and under the driver's protocol (--steps 20 --warmup 5)
+#   bench     bench.py --full with its defaults, and a plain run under the driver's protocol (--steps 20 --warmup 5)
 #   stats     rocprofv3 --kernel-trace --stats of bench.py (config 2, 0/1 data) and of the real-valued-data runs (grey / Bernoulli,
 #             grey / Gaussian: the reference's default mode)
 #   traffic   HBM bytes per launch: FETCH_SIZE and WRITE_SIZE in separate --pmc passes (MI355X_MICROARCH.md, HBM section)
@@ -16,7 +16,7 @@ PARTS=${*:-bench stats traffic sq score config5 small}
 O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
 has() { case " $PARTS " in *" $1 "*) return 0;; esac; return 1; }
 if has bench; then
-  python bench.py > $O/bench.json 2> $O/bench.err; tail -c 200 $O/bench.json; echo
+  python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 200 $O/bench.json; echo
   python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_protocol.json 2>> $O/bench.err
 fi
 if has stats; then
