@@ -11,6 +11,10 @@ Data: Kaggle `train.csv` / `test.csv` in the working directory if present (refer
 otherwise scikit-learn's bundled 8x8 digits, scaled to [0,1] and nearest-neighbour upsampled to
 28x28 = 784 pixels (MNIST itself is not available offline).  The RBM runs on the HIP kernels; the
 softmax head is a torch Linear layer on the same device (it is not part of the hot path).
+
+`rbm_hps` of the JSON config also takes `momentum` (a number, or a list indexed by epoch whose last value holds:
+[0.5, 0.5, 0.5, 0.5, 0.5, 0.9]) and `weight_decay` (on the scale of the batch SUMS that `lr` multiplies); both default to
+0, the reference's bare update rule.
 """
 import json
 import os

@@ -453,6 +453,56 @@ int kurbm_cd_step_x3_peer(kurbm_ctx* ctx, kurbm_peer* peer, const kurbm_params* 
                           size_t workspace_bytes, kurbm_stream_t stream);
 void kurbm_peer_destroy(kurbm_peer* peer);
 
+/* ---- momentum and L2 weight decay, fused into the launch that applies the update (extension) ----------------------
+ *
+ * The reference's rule is the bare theta += lr * sum_batch(pos - neg) (rbm.py:125-134).  The *_mom entry points apply the same
+ * packed sums g (v_pos^T h_pos - v_neg^T h_neg and the bias column sums: bit for bit what opts->delta_out receives from the plain
+ * step with the same counters) through a velocity, all in fp32:
+ *     W   : vel <- momentum * vel + lr * (g - weight_decay * W) ;  W   <- W   + vel
+ *     b_h : vel <- momentum * vel + lr * g                      ;  b_h <- b_h + vel      (no decay on biases; b_v likewise)
+ * lr multiplies batch SUMS, so weight_decay is on the scale of those sums, not of a per-row mean (a mean-gradient recipe's
+ * lambda times the batch size); the library does not rescale by the row count -- under data parallelism the apply sees only
+ * the sum.  `vel` is caller-owned device memory in the layout of delta_out, packed [n_vis*n_hid | n_hid | n_vis] fp32 with no row
+ * padding, 16-byte aligned, zeroed by the caller before the first step.  `which` masks as in kurbm_cd_step: a variable it does not
+ * select has neither its parameters nor its velocity read or written.  The padding columns of W stay zero.
+ * The velocity travels inside the launch that already reduces the slabs and rewrites the weights (and, on the x3 / bf16 paths,
+ * their bf16 pieces, which are made from the NEW weights): one more 16-byte load and store per weight group, no extra launch.
+ * Every *_mom entry point takes the arguments of its plain twin plus `mom`, requires opts->apply = 1 and honours
+ * opts->delta_out where the twin does (the same launch emits g).  KURBM_ERR_ARG, before anything is enqueued: mom or mom->vel null,
+ * vel misaligned, momentum outside [0, 1), weight_decay < 0.  n_hid % 4 != 0 (velocity rows not 16-byte aligned) is served by the
+ * two-launch form: update, then the mirror refresh.  The plain entry points are unchanged: they launch the kernels without any of this.
+ */
+typedef struct {
+    float momentum;      /* mu in [0, 1) */
+    float weight_decay;  /* lambda >= 0, on the scale of the batch sums */
+    float* vel;          /* packed [n_vis*n_hid | n_hid | n_vis], 16-byte aligned */
+} kurbm_momentum;
+
+/* kurbm_cd_step / kurbm_cd_step_x3 / kurbm_cd_step_bf16 with the update applied through the velocity. */
+int kurbm_cd_step_mom(kurbm_ctx* ctx, const kurbm_params* p, const float* v_batch, int rows, int ldv,
+                      const kurbm_cd_opts* opts, int which, void* workspace, size_t workspace_bytes,
+                      kurbm_stream_t stream, const kurbm_momentum* mom);
+int kurbm_cd_step_x3_mom(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t mirror_bytes, const float* v_batch,
+                         int v_pieces, int rows, int ldv, const kurbm_cd_opts* opts, int which, void* workspace,
+                         size_t workspace_bytes, kurbm_stream_t stream, const kurbm_momentum* mom);
+int kurbm_cd_step_bf16_mom(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t mirror_bytes, const float* v_batch,
+                           int rows, int ldv, const kurbm_cd_opts* opts, int which, void* workspace, size_t workspace_bytes,
+                           kurbm_stream_t stream, const kurbm_momentum* mom);
+/* kurbm_cd_epoch / kurbm_cd_epoch_x3 likewise: one momentum and one weight_decay for every step of the call (a schedule over
+ * epochs is the caller's: one call per epoch).  Returns the number of steps. */
+int kurbm_cd_epoch_mom(kurbm_ctx* ctx, const kurbm_params* p, const float* V, int n_rows, int ldv, int batch_size,
+                       const kurbm_cd_opts* opts, void* workspace, size_t workspace_bytes, kurbm_stream_t stream,
+                       const kurbm_momentum* mom);
+int kurbm_cd_epoch_x3_mom(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t mirror_bytes, const float* V,
+                          int v_pieces, int n_rows, int ldv, int batch_size, const kurbm_cd_opts* opts, void* workspace,
+                          size_t workspace_bytes, kurbm_stream_t stream, const kurbm_momentum* mom);
+/* kurbm_apply_delta / kurbm_x3_apply_delta likewise: the apply after a data-parallel exchange, g = the summed packed delta.  The
+ * summed delta is the same on every rank, so the replicas' velocities stay identical. */
+int kurbm_apply_delta_mom(kurbm_ctx* ctx, const kurbm_params* p, const float* delta, float lr, int which,
+                          kurbm_stream_t stream, const kurbm_momentum* mom);
+int kurbm_x3_apply_delta_mom(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t mirror_bytes, const float* delta,
+                             float lr, int which, kurbm_stream_t stream, const kurbm_momentum* mom);
+
 /* *flag (device int, zeroed by the caller) |= 1 if some element of x [rows][ld] is not exactly representable in bf16,
  * |= 2 if some element is neither 0.0 nor 1.0.  0: v_pieces = 1 | KURBM_V_BINARY; 2: v_pieces = 1; else 3. */
 int kurbm_bf16_exact(kurbm_ctx* ctx, const float* x, int rows, int cols, int ld, int* flag,

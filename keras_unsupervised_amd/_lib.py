@@ -37,8 +37,13 @@ class CdOpts(C.Structure):
                 ("v_planes", C.c_void_p), ("v_planes_stride", C.c_uint64)]
 
 
+class Momentum(C.Structure):
+    """kurbm_momentum: vel <- momentum vel + lr (g - weight_decay W); W += vel (include/kurbm.h)."""
+    _fields_ = [("momentum", C.c_float), ("weight_decay", C.c_float), ("vel", C.c_void_p)]
+
+
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
-_PP, _RP, _OP = C.POINTER(Params), C.POINTER(Rng), C.POINTER(CdOpts)
+_PP, _RP, _OP, _MP = C.POINTER(Params), C.POINTER(Rng), C.POINTER(CdOpts), C.POINTER(Momentum)
 
 # name -> (restype, argtypes); every symbol include/kurbm.h declares
 SIGNATURES = {
@@ -102,6 +107,14 @@ SIGNATURES = {
     "kurbm_peer_allreduce_sum_f32": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "kurbm_cd_step_x3_peer": (_i, [_vp, _vp, _PP, _vp, _sz, _vp, _i, _i, _i, _OP, _vp, _sz, _vp]),
     "kurbm_peer_destroy": (None, [_vp]),
+    # the plain twins' arguments + const kurbm_momentum*
+    "kurbm_cd_step_mom": (_i, [_vp, _PP, _vp, _i, _i, _OP, _i, _vp, _sz, _vp, _MP]),
+    "kurbm_cd_step_x3_mom": (_i, [_vp, _PP, _vp, _sz, _vp, _i, _i, _i, _OP, _i, _vp, _sz, _vp, _MP]),
+    "kurbm_cd_step_bf16_mom": (_i, [_vp, _PP, _vp, _sz, _vp, _i, _i, _OP, _i, _vp, _sz, _vp, _MP]),
+    "kurbm_cd_epoch_mom": (_i, [_vp, _PP, _vp, _i, _i, _i, _OP, _vp, _sz, _vp, _MP]),
+    "kurbm_cd_epoch_x3_mom": (_i, [_vp, _PP, _vp, _sz, _vp, _i, _i, _i, _i, _OP, _vp, _sz, _vp, _MP]),
+    "kurbm_apply_delta_mom": (_i, [_vp, _PP, _vp, C.c_float, _i, _vp, _MP]),
+    "kurbm_x3_apply_delta_mom": (_i, [_vp, _PP, _vp, _sz, _vp, C.c_float, _i, _vp, _MP]),
 }
 
 ABI_VERSION = 5

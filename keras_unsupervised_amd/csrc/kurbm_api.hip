@@ -117,6 +117,24 @@ static int check_params(const kurbm_params* p) {
     return KURBM_OK;
 }
 
+// Momentum / weight decay of the *_mom entry points (include/kurbm.h): refused here, before anything is enqueued
+static int check_mom(const kurbm_momentum* m, const kurbm_cd_opts* o) {
+    if (!m || !m->vel) return fail(KURBM_ERR_ARG, "momentum block or its velocity buffer is null");
+    if (!aligned16(m->vel)) return fail(KURBM_ERR_ARG, "the velocity buffer is not 16-byte aligned");
+    if (!(m->momentum >= 0.f && m->momentum < 1.f)) return fail(KURBM_ERR_ARG, "momentum must be in [0, 1), got %g", (double)m->momentum);
+    if (!(m->weight_decay >= 0.f)) return fail(KURBM_ERR_ARG, "weight_decay must be >= 0, got %g", (double)m->weight_decay);
+    if (o && !o->apply) return fail(KURBM_ERR_ARG, "the momentum entry points apply the update in place: apply = 1");
+    return KURBM_OK;
+}
+// ... as the kernels take it: the three velocities of the packed buffer, W's from visible row m_lo on
+static MomArgs make_mom(const kurbm_params* p, const kurbm_momentum* m, int m_lo = 0) {
+    MomArgs mo;
+    const size_t nw = (size_t)p->n_vis * p->n_hid;
+    mo.mu = m->momentum; mo.decay = m->weight_decay;
+    mo.vel_w = m->vel + (size_t)m_lo * p->n_hid; mo.vel_bh = m->vel + nw; mo.vel_bv = m->vel + nw + p->n_hid;
+    return mo;
+}
+
 static RngArgs make_rng(uint64_t seed, uint64_t row0, uint32_t stream_id, uint32_t step) {
     RngArgs r;
     r.seed_lo = (uint32_t)(seed & 0xFFFFFFFFu);
@@ -425,8 +443,10 @@ size_t kurbm_workspace_bytes(kurbm_ctx* ctx, int rows, int n_vis, int n_hid, int
     return carve(ctx, nullptr, rows, n_vis, n_hid, k).bytes;
 }
 
-int kurbm_cd_step(kurbm_ctx* ctx, const kurbm_params* p, const float* v_batch, int rows, int ldv,
-                  const kurbm_cd_opts* o, int which, void* workspace, size_t workspace_bytes, kurbm_stream_t stream) {
+// (mom: null = the reference's bare rule on the ordinary kernels; else kurbm_cd_step_mom)
+static int cd_step_f32(kurbm_ctx* ctx, const kurbm_params* p, const float* v_batch, int rows, int ldv,
+                       const kurbm_cd_opts* o, int which, void* workspace, size_t workspace_bytes, kurbm_stream_t stream,
+                       const kurbm_momentum* mom) {
     if (!ctx || !o) return fail(KURBM_ERR_ARG, "null argument");
     if (int e = check_params(p)) return e;
     if (rows <= 0) return fail(KURBM_ERR_ARG, "rows must be positive");
@@ -515,8 +535,24 @@ int kurbm_cd_step(kurbm_ctx* ctx, const kurbm_params* p, const float* v_batch, i
     a.part_v = w.part_v; a.nrow_tiles_v = gm_v; a.ld_part_v = w.ld_part_v;
     a.b_v = (ap && (which & 4)) ? p->b_v : nullptr;
     a.delta_bv = o->delta_out ? o->delta_out + (size_t)p->n_vis * p->n_hid + p->n_hid : nullptr;
-    HIP_TRY(launch_reduce_apply(a, st));
+    if (mom) {
+        const MomArgs mo = make_mom(p, mom);
+        HIP_TRY(launch_reduce_apply(a, st, &mo));
+    } else HIP_TRY(launch_reduce_apply(a, st));
     return KURBM_OK;
+}
+
+int kurbm_cd_step(kurbm_ctx* ctx, const kurbm_params* p, const float* v_batch, int rows, int ldv,
+                  const kurbm_cd_opts* o, int which, void* workspace, size_t workspace_bytes, kurbm_stream_t stream) {
+    return cd_step_f32(ctx, p, v_batch, rows, ldv, o, which, workspace, workspace_bytes, stream, nullptr);
+}
+
+int kurbm_cd_step_mom(kurbm_ctx* ctx, const kurbm_params* p, const float* v_batch, int rows, int ldv,
+                      const kurbm_cd_opts* o, int which, void* workspace, size_t workspace_bytes, kurbm_stream_t stream,
+                      const kurbm_momentum* mom) {
+    if (!o) return fail(KURBM_ERR_ARG, "null argument");
+    if (int e = check_mom(mom, o)) return e;
+    return cd_step_f32(ctx, p, v_batch, rows, ldv, o, which, workspace, workspace_bytes, stream, mom);
 }
 
 // One CD-1 update of a small RBM in ONE launch (kurbm_small.hip).  Workspace as kurbm_cd_step (kurbm_workspace_bytes).
@@ -635,8 +671,9 @@ int kurbm_cd_epoch_small(kurbm_ctx* ctx, const kurbm_params* p, const float* V, 
     return steps;
 }
 
-int kurbm_cd_epoch(kurbm_ctx* ctx, const kurbm_params* p, const float* V, int n_rows, int ldv, int batch_size,
-                   const kurbm_cd_opts* opts, void* workspace, size_t workspace_bytes, kurbm_stream_t stream) {
+static int cd_epoch_f32(kurbm_ctx* ctx, const kurbm_params* p, const float* V, int n_rows, int ldv, int batch_size,
+                        const kurbm_cd_opts* opts, void* workspace, size_t workspace_bytes, kurbm_stream_t stream,
+                        const kurbm_momentum* mom) {
     if (!ctx || !opts) return fail(KURBM_ERR_ARG, "null argument");
     if (n_rows < 0 || batch_size <= 0) return fail(KURBM_ERR_ARG, "bad row count / batch size");
     if (opts->delta_out || !opts->apply) return fail(KURBM_ERR_ARG, "kurbm_cd_epoch applies in place: apply = 1, delta_out = null");
@@ -644,14 +681,27 @@ int kurbm_cd_epoch(kurbm_ctx* ctx, const kurbm_params* p, const float* V, int n_
     int steps = 0;
     for (int lo = 0; lo < n_rows; lo += batch_size, ++steps) {
         const int rows = (n_rows - lo < batch_size) ? n_rows - lo : batch_size;
-        if (int e = kurbm_cd_step(ctx, p, V + (size_t)lo * ldv, rows, ldv, &o, 7, workspace, workspace_bytes, stream)) return e;
+        if (int e = cd_step_f32(ctx, p, V + (size_t)lo * ldv, rows, ldv, &o, 7, workspace, workspace_bytes, stream, mom)) return e;
         ++o.step;
     }
     return steps;
 }
 
-int kurbm_apply_delta(kurbm_ctx* ctx, const kurbm_params* p, const float* delta, float lr, int which,
-                      kurbm_stream_t stream) {
+int kurbm_cd_epoch(kurbm_ctx* ctx, const kurbm_params* p, const float* V, int n_rows, int ldv, int batch_size,
+                   const kurbm_cd_opts* opts, void* workspace, size_t workspace_bytes, kurbm_stream_t stream) {
+    return cd_epoch_f32(ctx, p, V, n_rows, ldv, batch_size, opts, workspace, workspace_bytes, stream, nullptr);
+}
+
+int kurbm_cd_epoch_mom(kurbm_ctx* ctx, const kurbm_params* p, const float* V, int n_rows, int ldv, int batch_size,
+                       const kurbm_cd_opts* opts, void* workspace, size_t workspace_bytes, kurbm_stream_t stream,
+                       const kurbm_momentum* mom) {
+    if (!opts) return fail(KURBM_ERR_ARG, "null argument");
+    if (int e = check_mom(mom, opts)) return e;
+    return cd_epoch_f32(ctx, p, V, n_rows, ldv, batch_size, opts, workspace, workspace_bytes, stream, mom);
+}
+
+static int apply_delta_f32(kurbm_ctx* ctx, const kurbm_params* p, const float* delta, float lr, int which,
+                           kurbm_stream_t stream, const kurbm_momentum* mom) {
     if (!ctx || !delta) return fail(KURBM_ERR_ARG, "null argument");
     if (int e = check_params(p)) return e;
     ApplyArgs a;
@@ -660,8 +710,22 @@ int kurbm_apply_delta(kurbm_ctx* ctx, const kurbm_params* p, const float* delta,
     a.b_h = (which & 2) ? p->b_h : nullptr;
     a.b_v = (which & 4) ? p->b_v : nullptr;
     a.n_vis = p->n_vis; a.n_hid = p->n_hid; a.ldw = p->ldw; a.lr = lr;
-    HIP_TRY(launch_apply_delta(a, static_cast<hipStream_t>(stream)));
+    if (mom) {
+        const MomArgs mo = make_mom(p, mom);
+        HIP_TRY(launch_apply_delta(a, static_cast<hipStream_t>(stream), &mo));
+    } else HIP_TRY(launch_apply_delta(a, static_cast<hipStream_t>(stream)));
     return KURBM_OK;
+}
+
+int kurbm_apply_delta(kurbm_ctx* ctx, const kurbm_params* p, const float* delta, float lr, int which,
+                      kurbm_stream_t stream) {
+    return apply_delta_f32(ctx, p, delta, lr, which, stream, nullptr);
+}
+
+int kurbm_apply_delta_mom(kurbm_ctx* ctx, const kurbm_params* p, const float* delta, float lr, int which,
+                          kurbm_stream_t stream, const kurbm_momentum* mom) {
+    if (int e = check_mom(mom, nullptr)) return e;
+    return apply_delta_f32(ctx, p, delta, lr, which, stream, mom);
 }
 
 int kurbm_free_energy(kurbm_ctx* ctx, const kurbm_params* p, const float* v, int rows, int ldv, float* F,
@@ -1102,7 +1166,9 @@ static bool atr_on(const kurbm_ctx* ctx, int pieces, int v_pieces, bool gauss) {
 
 static int cd_step_any(kurbm_ctx* ctx, int pieces, int v_pieces, const kurbm_params* p, void* mirror, size_t mirror_bytes,
                        const float* v_batch, int rows, int ldv, const kurbm_cd_opts* o, int which, void* workspace,
-                       size_t workspace_bytes, kurbm_stream_t stream, int only = -1, int m_lo = 0, int m_hi = -1) {
+                       size_t workspace_bytes, kurbm_stream_t stream, int only = -1, int m_lo = 0, int m_hi = -1,
+                       const kurbm_momentum* mom = nullptr) {
+    // mom (nullable; whole steps only): the update goes through the velocity, in the same launch (kurbm_cd_step_x3_mom, _bf16_mom).
     // `only` 0..6 (measurement hook kurbm_cd_step_x3_stage): launch just that stage of the sequence, on the planes a
     // previous complete step left in the workspace.  8: the chain alone (stages 0-3, kurbm_cd_chain_x3).  7: the
     // statistics of visible rows [m_lo, m_hi) alone (stages 4-5, kurbm_x3_stats_rows) -- the data-parallel step
@@ -1110,6 +1176,10 @@ static int cd_step_any(kurbm_ctx* ctx, int pieces, int v_pieces, const kurbm_par
 #define KURBM_STAGE(n) (only < 0 || only == (n) || (only == 8 && (n) <= 3) || (only == 7 && ((n) == 4 || (n) == 5)))
     if (m_hi < 0) m_hi = p ? p->n_vis : 0;
     if (int e = check_cd_args(ctx, pieces, v_pieces, p, mirror, mirror_bytes, v_batch, rows, ldv, o, workspace, workspace_bytes, false)) return e;
+    if (mom) {
+        if (int e = check_mom(mom, o)) return e;
+        if (only >= 0) return fail(KURBM_ERR_ARG, "momentum applies to whole steps only");
+    }
     const bool v_binary = (v_pieces == (1 | KURBM_V_BINARY));
     if (v_binary) v_pieces = 1;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1248,7 +1318,10 @@ static int cd_step_any(kurbm_ctx* ctx, int pieces, int v_pieces, const kurbm_par
     a.delta_bv = o->delta_out ? o->delta_out + (size_t)p->n_vis * p->n_hid + p->n_hid : nullptr;
     if (sub && m_hi != p->n_vis) { a.part_h = nullptr; a.part_v = nullptr; a.part_v2 = nullptr; }   // the bias sums leave with the LAST rows
     if (sub) a.n_vis_bias = p->n_vis;
-    const bool mirror_in_reduce = a.W && need_w && !ctx->knob[KN_UNFUSED_MIRROR];
+    // (the velocity rows of an n_hid that is no multiple of 4 are not 16-byte aligned: the two-launch form serves them)
+    const bool mirror_in_reduce = a.W && need_w && !ctx->knob[KN_UNFUSED_MIRROR] && !(mom && (p->n_hid & 3));
+    MomArgs mo;
+    if (mom) mo = make_mom(p, mom);
     if (mirror_in_reduce) {
         // the fp32 master moves: the slab reduction writes the new weights AND their bf16 pieces in one pass
         a.Wb = m.Wb; a.ldWb = m.ldW; a.planeWb = m.planeW;
@@ -1325,12 +1398,12 @@ static int cd_step_any(kurbm_ctx* ctx, int pieces, int v_pieces, const kurbm_par
         HIP_TRY(launch_gemm_pb(EPI_SLAB, g, st));
     }
     if (mirror_in_reduce) {
-        if (KURBM_STAGE(5)) HIP_TRY(launch_reduce_apply_split(a, st));
+        if (KURBM_STAGE(5)) HIP_TRY(launch_reduce_apply_split(a, st, nullptr, mom ? &mo : nullptr));
         if (only == 6)
             HIP_TRY(launch_f32_to_bf16(p->W, p->n_vis, p->n_hid, p->ldw, m.Wb, m.ldW, p->n_vis, m.Wtb, m.ldWt, p->n_hid, pieces,
                                        m.planeW, m.planeWt, nullptr, 0, st));
     } else {
-        if (KURBM_STAGE(5)) HIP_TRY(launch_reduce_apply(a, st));
+        if (KURBM_STAGE(5)) HIP_TRY(launch_reduce_apply(a, st, mom ? &mo : nullptr));
         if (a.W && (KURBM_STAGE(5) || only == 6))   // the fp32 master moved: re-derive both mirrors
             HIP_TRY(launch_f32_to_bf16(p->W, p->n_vis, p->n_hid, p->ldw, m.Wb, m.ldW, p->n_vis, m.Wtb, m.ldWt, p->n_hid, pieces,
                                        m.planeW, m.planeWt, nullptr, 0, st));
@@ -1393,6 +1466,20 @@ int kurbm_cd_step_x3(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t
                      int v_pieces, int rows, int ldv, const kurbm_cd_opts* o, int which, void* workspace,
                      size_t workspace_bytes, kurbm_stream_t stream) {
     return cd_step_any(ctx, 3, v_pieces, p, mirror, mirror_bytes, v_batch, rows, ldv, o, which, workspace, workspace_bytes, stream);
+}
+
+int kurbm_cd_step_bf16_mom(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t mirror_bytes, const float* v_batch,
+                           int rows, int ldv, const kurbm_cd_opts* o, int which, void* workspace, size_t workspace_bytes,
+                           kurbm_stream_t stream, const kurbm_momentum* mom) {
+    if (!mom) return fail(KURBM_ERR_ARG, "momentum block or its velocity buffer is null");
+    return cd_step_any(ctx, 1, 1, p, mirror, mirror_bytes, v_batch, rows, ldv, o, which, workspace, workspace_bytes, stream, -1, 0, -1, mom);
+}
+int kurbm_cd_step_x3_mom(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t mirror_bytes, const float* v_batch,
+                         int v_pieces, int rows, int ldv, const kurbm_cd_opts* o, int which, void* workspace,
+                         size_t workspace_bytes, kurbm_stream_t stream, const kurbm_momentum* mom) {
+    if (!mom) return fail(KURBM_ERR_ARG, "momentum block or its velocity buffer is null");
+    return cd_step_any(ctx, 3, v_pieces, p, mirror, mirror_bytes, v_batch, rows, ldv, o, which, workspace, workspace_bytes, stream, -1, 0, -1,
+                       mom);
 }
 
 int kurbm_cd_step_x3_stage(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t mirror_bytes, const float* v_batch,
@@ -1553,9 +1640,9 @@ int kurbm_x3_dump_plane(kurbm_ctx* ctx, int which, int rows, int n_vis, int n_hi
     return KURBM_OK;
 }
 
-int kurbm_cd_epoch_x3(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t mirror_bytes, const float* V,
-                      int v_pieces, int n_rows, int ldv, int batch_size, const kurbm_cd_opts* opts, void* workspace,
-                      size_t workspace_bytes, kurbm_stream_t stream) {
+static int cd_epoch_x3_any(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t mirror_bytes, const float* V,
+                           int v_pieces, int n_rows, int ldv, int batch_size, const kurbm_cd_opts* opts, void* workspace,
+                           size_t workspace_bytes, kurbm_stream_t stream, const kurbm_momentum* mom) {
     if (!ctx || !opts) return fail(KURBM_ERR_ARG, "null argument");
     if (n_rows < 0 || batch_size <= 0) return fail(KURBM_ERR_ARG, "bad row count / batch size");
     if (opts->delta_out || !opts->apply) return fail(KURBM_ERR_ARG, "kurbm_cd_epoch_x3 applies in place: apply = 1, delta_out = null");
@@ -1568,11 +1655,25 @@ int kurbm_cd_epoch_x3(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_
         const int rows = (n_rows - lo < batch_size) ? n_rows - lo : batch_size;
         if (opts->v_planes) o.v_planes = static_cast<const char*>(opts->v_planes) + (size_t)steps * opts->v_planes_stride;
         if (int e = cd_step_any(ctx, 3, v_pieces, p, mirror, mirror_bytes, V + (size_t)lo * ldv, rows, ldv, &o, 7, workspace,
-                                workspace_bytes, stream))
+                                workspace_bytes, stream, -1, 0, -1, mom))
             return e;
         ++o.step;
     }
     return steps;
+}
+
+int kurbm_cd_epoch_x3(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t mirror_bytes, const float* V,
+                      int v_pieces, int n_rows, int ldv, int batch_size, const kurbm_cd_opts* opts, void* workspace,
+                      size_t workspace_bytes, kurbm_stream_t stream) {
+    return cd_epoch_x3_any(ctx, p, mirror, mirror_bytes, V, v_pieces, n_rows, ldv, batch_size, opts, workspace, workspace_bytes, stream, nullptr);
+}
+
+int kurbm_cd_epoch_x3_mom(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t mirror_bytes, const float* V,
+                          int v_pieces, int n_rows, int ldv, int batch_size, const kurbm_cd_opts* opts, void* workspace,
+                          size_t workspace_bytes, kurbm_stream_t stream, const kurbm_momentum* mom) {
+    if (!opts) return fail(KURBM_ERR_ARG, "null argument");
+    if (int e = check_mom(mom, opts)) return e;
+    return cd_epoch_x3_any(ctx, p, mirror, mirror_bytes, V, v_pieces, n_rows, ldv, batch_size, opts, workspace, workspace_bytes, stream, mom);
 }
 
 int kurbm_cd_chain_x3(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t mirror_bytes, const float* v_batch,
@@ -1595,7 +1696,7 @@ int kurbm_x3_stats_rows(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, siz
 // W (rows [m_lo, m_hi)), and with `bias` b_h and b_v, += lr * (packed delta); the bf16 pieces of the new weights rewritten
 // in both orientations -- one launch: the packed delta is one "slab" and one row of bias partials each.
 static int apply_delta_rows(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t mirror_bytes, int pieces, const float* delta,
-                            float lr, int which, int m_lo, int m_hi, bool bias, hipStream_t st) {
+                            float lr, int which, int m_lo, int m_hi, bool bias, hipStream_t st, const kurbm_momentum* mom = nullptr) {
     const Mirror m = carve_mirror(ctx, mirror, p->n_vis, p->n_hid, pieces);
     if (m.bytes > mirror_bytes) return fail(KURBM_ERR_WORKSPACE, "mirror too small: need %zu bytes, got %zu", m.bytes, mirror_bytes);
     ReduceArgs a;
@@ -1613,7 +1714,10 @@ static int apply_delta_rows(kurbm_ctx* ctx, const kurbm_params* p, void* mirror,
     // the transposed mirror's k columns of these rows; the last range also rewrites the zero k padding behind n_vis
     a.wtb_k_ext = (m_hi == p->n_vis) ? m.ldWt - m_lo : m_hi - m_lo;
     a.tile_rows = ctx->knob[KN_REDUCE_TR];
-    HIP_TRY(launch_reduce_apply_split(a, st));
+    if (mom) {
+        const MomArgs mo = make_mom(p, mom, m_lo);
+        HIP_TRY(launch_reduce_apply_split(a, st, nullptr, &mo));
+    } else HIP_TRY(launch_reduce_apply_split(a, st));
     return KURBM_OK;
 }
 
@@ -1755,8 +1859,8 @@ int kurbm_cd_step_bf16_dp(kurbm_ctx* ctx, kurbm_comm* comm, const kurbm_params* 
     return cd_step_dp_any(ctx, comm, 1, p, mirror, mirror_bytes, v_batch, 1, rows, ldv, opts, n_chunks, workspace, workspace_bytes, stream);
 }
 
-int kurbm_x3_apply_delta(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t mirror_bytes, const float* delta,
-                         float lr, int which, kurbm_stream_t stream) {
+static int x3_apply_delta_any(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t mirror_bytes, const float* delta,
+                              float lr, int which, kurbm_stream_t stream, const kurbm_momentum* mom) {
     if (!ctx || !delta) return fail(KURBM_ERR_ARG, "null argument");
     if (int e = check_params(p)) return e;
     if (!mirror || !aligned16(mirror) || !aligned16(delta)) return fail(KURBM_ERR_ARG, "mirror / delta null or misaligned");
@@ -1764,13 +1868,24 @@ int kurbm_x3_apply_delta(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, si
     if ((p->n_hid & 3) || !(which & 1)) {   // packed rows not 16-byte aligned, or W untouched: two launches
         const Mirror m = carve_mirror(ctx, mirror, p->n_vis, p->n_hid, 3);
         if (m.bytes > mirror_bytes) return fail(KURBM_ERR_WORKSPACE, "mirror too small: need %zu bytes, got %zu", m.bytes, mirror_bytes);
-        if (int e = kurbm_apply_delta(ctx, p, delta, lr, which, stream)) return e;
+        if (int e = apply_delta_f32(ctx, p, delta, lr, which, stream, mom)) return e;
         if (which & 1)
             HIP_TRY(launch_f32_to_bf16(p->W, p->n_vis, p->n_hid, p->ldw, m.Wb, m.ldW, p->n_vis, m.Wtb, m.ldWt, p->n_hid, 3,
                                        m.planeW, m.planeWt, nullptr, 0, st));
         return KURBM_OK;
     }
-    return apply_delta_rows(ctx, p, mirror, mirror_bytes, 3, delta, lr, which, 0, p->n_vis, true, st);
+    return apply_delta_rows(ctx, p, mirror, mirror_bytes, 3, delta, lr, which, 0, p->n_vis, true, st, mom);
+}
+
+int kurbm_x3_apply_delta(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t mirror_bytes, const float* delta,
+                         float lr, int which, kurbm_stream_t stream) {
+    return x3_apply_delta_any(ctx, p, mirror, mirror_bytes, delta, lr, which, stream, nullptr);
+}
+
+int kurbm_x3_apply_delta_mom(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t mirror_bytes, const float* delta,
+                             float lr, int which, kurbm_stream_t stream, const kurbm_momentum* mom) {
+    if (int e = check_mom(mom, nullptr)) return e;
+    return x3_apply_delta_any(ctx, p, mirror, mirror_bytes, delta, lr, which, stream, mom);
 }
 
 size_t kurbm_x3_planes_bytes(kurbm_ctx* ctx, int rows, int n_vis, int v_pieces) {

@@ -28,6 +28,7 @@
 
 #include "kurbm_kernels.h"
 #include "kurbm_device.h"
+#include "kurbm_reduce.h"
 
 namespace kurbm {
 
@@ -43,7 +44,6 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // Out-of-range source elements read as zero, so the k padding of both mirrors is written here and
 // nowhere else.  pieces = 3 writes the exact split x = hi + mid + lo (bf16_piece_bits) as three planes.
 // colpart (nullable): column sums of each 64-row band of `in`.
-constexpr int CVT = 64;
 template <int TR>
 __global__ __launch_bounds__(256) void k_f32_to_bf16(const float* __restrict__ in, int rows, int cols, int ld_in,
                                                      uint16_t* __restrict__ out, int ldo, int out_rows,
@@ -190,152 +190,23 @@ __global__ __launch_bounds__(256) void k_f32_to_planes01(const float* __restrict
 // buffers (kurbm_peer.hip) -- the rows of band q from rank q's `sum` region once its `summed` flag is up: the all-gather of the
 // two-shot all-reduce IS this launch's read.  Workgroup 0 also waits for EVERY rank's flag (a rank with an empty band still read
 // this rank's bias tail: nobody's `delta` may be rewritten before all are done).
-template <int TR, bool PEER>
-__device__ __forceinline__ void reduce_apply_split_body(ReduceArgs& a, int tiles_x, int tiles, int nbias, const PeerSrc& ps) {
-    __shared__ __attribute__((aligned(16))) float tile[TR][CVT + 1];
-    __shared__ int peer_ok;
-    const int t = threadIdx.x;
-    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-    if constexpr (PEER) {
-        if (blockIdx.x == 0) {
-            if (t == 0) peer_ok = 1;
-            __syncthreads();
-            if (t < ps.nranks && !wait_flag_ge(ps.summed[t], ps.epoch, ps.timeout_ticks)) peer_ok = 0;
-            __syncthreads();
-            if (!peer_ok) {
-                if (t == 0) __hip_atomic_fetch_or(ps.status, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                return;
-            }
-        }
-    }
-    // the first nbias blocks: bias column sums (kurbm_kernels.h); then the tiles of W
-    if ((int)blockIdx.x < nbias) {
-        bias_colsum_wave(a, blockIdx.x * 4 + (t >> 6), t & 63);
-        return;
-    }
-    const int tb = (int)blockIdx.x - nbias;
-    if (tb < tiles) {
-        const int by = tb / tiles_x, bx = tb - by * tiles_x;
-        if constexpr (PEER) {
-            // the band of this tile's rows (band_rows is a multiple of TR; tiles past the matrix only write mirror padding)
-            int q = (by * TR) / ps.band_rows;
-            if (q >= ps.nranks) q = ps.nranks - 1;
-            if (t == 0) peer_ok = (by * TR >= a.n_vis || wait_flag_ge(ps.summed[q], ps.epoch, ps.timeout_ticks)) ? 1 : 0;
-            __syncthreads();
-            if (!peer_ok) {
-                if (t == 0) __hip_atomic_fetch_or(ps.status, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                return;
-            }
-            a.slab = ps.sum[q];      // (nslab = 1, ld_slab = n_hid: the packed layout)
-        }
-        const int q4 = (t & 15) * 4, rq = t >> 4;
-        const int c = bx * CVT + q4;
-        auto store3 = [&](uint16_t* dst, size_t plane, float v0, float v1, float v2, float v3) {
-            float v[4] = {v0, v1, v2, v3};
-            for (int j = 0; j < a.pieces; ++j) {
-                u32x2 pk;
-                pk.x = pack_bf16x2(v[0], v[1]); pk.y = pack_bf16x2(v[2], v[3]);
-                *reinterpret_cast<u32x2*>(dst + j * plane) = pk;
-                if (j + 1 < a.pieces) {
-                    v[0] -= bf16_bits_to_f32(pk.x & 0xFFFFu); v[1] -= bf16_bits_to_f32(pk.x >> 16);
-                    v[2] -= bf16_bits_to_f32(pk.y & 0xFFFFu); v[3] -= bf16_bits_to_f32(pk.y >> 16);
-                }
-            }
-        };
-        // Every load of the thread's TR / 16 rows goes out before the first sum: the rows' weights and their first four slabs (this launch
-        // is a burst of ~17 MB of loads that every CU must keep in flight: with the rows one after the other a wave held 5 x 16 bytes per
-        // lane in flight, now TR / 16 times that).  The slabs are still added in slab order, row by row: the same bits as before.
-        constexpr int NJ = TR / 16;
-        f32x4 wv[NJ], sv[NJ][4];
-        bool live[NJ];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int r = by * TR + rq + 16 * j;
-            live[j] = r < a.n_vis && c < a.n_hid;
-            wv[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int z = 0; z < 4; ++z) sv[j][z] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (live[j]) {
-                if (a.W) wv[j] = *reinterpret_cast<const f32x4*>(a.W + (size_t)r * a.ldw + c);           // ldw % 4 == 0
-                if (a.slab) {
-                    const float* sp = a.slab + (size_t)r * a.ld_slab + c;    // ld_slab % 4 == 0: the group stays inside the row
-#pragma unroll
-                    for (int z = 0; z < 4; ++z)
-                        if (z < a.nslab) sv[j][z] = *reinterpret_cast<const f32x4*>(sp + (size_t)z * a.slab_stride);
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int r = by * TR + rq + 16 * j;
-            f32x4 w = {0.f, 0.f, 0.f, 0.f};
-            if (live[j]) {
-                f32x4 s = {0.f, 0.f, 0.f, 0.f};
-                if (a.slab) {
-                    const float* sp = a.slab + (size_t)r * a.ld_slab + c;
-#pragma unroll
-                    for (int z = 0; z < 4; ++z)
-                        if (z < a.nslab) s += sv[j][z];
-                    int zz = 4;
-                    for (; zz + 4 <= a.nslab; zz += 4) {
-                        const f32x4 v0 = *reinterpret_cast<const f32x4*>(sp + (size_t)(zz + 0) * a.slab_stride);
-                        const f32x4 v1 = *reinterpret_cast<const f32x4*>(sp + (size_t)(zz + 1) * a.slab_stride);
-                        const f32x4 v2 = *reinterpret_cast<const f32x4*>(sp + (size_t)(zz + 2) * a.slab_stride);
-                        const f32x4 v3 = *reinterpret_cast<const f32x4*>(sp + (size_t)(zz + 3) * a.slab_stride);
-                        s += v0; s += v1; s += v2; s += v3;
-                    }
-                    for (; zz < a.nslab; ++zz) s += *reinterpret_cast<const f32x4*>(sp + (size_t)zz * a.slab_stride);
-                }
-                if (a.W) {
-                    float* wp = a.W + (size_t)r * a.ldw + c;
-                    w = wv[j];
-                    if (a.slab) w = w + s * a.lr;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (c + e >= a.n_hid) w[e] = 0.f;                     // the row padding stays zero
-                    if (a.slab) *reinterpret_cast<f32x4*>(wp) = w;
-                }
-                if (a.delta_w) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (c + e < a.n_hid) a.delta_w[(size_t)r * a.n_hid + c + e] = s[e];
-                }
-            }
-            tile[rq + 16 * j][q4 + 0] = w.x; tile[rq + 16 * j][q4 + 1] = w.y;
-            tile[rq + 16 * j][q4 + 2] = w.z; tile[rq + 16 * j][q4 + 3] = w.w;
-            if (a.Wb && r < a.n_vis && c < a.ldWb) store3(a.Wb + (size_t)r * a.ldWb + c, a.planeWb, w.x, w.y, w.z, w.w);
-        }
-        __syncthreads();
-        if (a.Wtb) {
-            // TR / 4 lanes x 4 rows down a column of the tile (a run of 2 TR bytes per column), 1024 / TR columns per pass
-            constexpr int LPC = TR / 4, CPP = 256 / LPC;
-            const int rr4 = (t % LPC) * 4, cq = t / LPC;
-            const int rr = by * TR + rr4;
-#pragma unroll
-            for (int j = 0; j < CVT / CPP; ++j) {
-                const int cl = cq + CPP * j, cc = bx * CVT + cl;
-                if (cc < a.n_hid && rr < (a.wtb_k_ext ? a.wtb_k_ext : a.ldWtb))
-                    store3(a.Wtb + (size_t)cc * a.ldWtb + rr, a.planeWtb, tile[rr4 + 0][cl], tile[rr4 + 1][cl], tile[rr4 + 2][cl],
-                           tile[rr4 + 3][cl]);
-            }
-        }
-        return;
-    }
-}
+// MOM (likewise a template flag): momentum and weight decay (kurbm_kernels.h: MomArgs) -- the velocity group of each row is loaded
+// with the row's weights, vel = mu vel + lr (dW - decay W) is stored, W += vel, and the bf16 pieces are made from that new W.  The
+// launcher admits it only where every group of the dense velocity is 16-byte aligned (n_hid % 4 == 0) and W is updated from slabs.
 // (two entry points: the ordinary launch does not carry the 184 bytes of peer pointers in its argument segment)
+// (the body, reduce_apply_split_body<TR, PEER, MOM>, is in kurbm_reduce.h: the MOM kernels are instantiated in kurbm_mom.hip)
 template <int TR>
 __global__ __launch_bounds__(256) void k_reduce_apply_split(ReduceArgs a, int tiles_x, int tiles, int nbias) {
     warm_kernel_arguments<sizeof(ReduceArgs) + 16>();   // (kurbm_device.h: one wait for the argument segment, not one per use)
     PeerSrc none;
     none.band_rows = 0;
-    reduce_apply_split_body<TR, false>(a, tiles_x, tiles, nbias, none);
+    reduce_apply_split_body<TR, false, false>(a, tiles_x, tiles, nbias, none, MomArgs{});
 }
 template <int TR>
 __global__ __launch_bounds__(256) void k_reduce_apply_split_peer(ReduceArgs a, int tiles_x, int tiles, int nbias, PeerSrc ps) {
     warm_kernel_arguments<sizeof(ReduceArgs) + 16 + sizeof(PeerSrc)>();
-    reduce_apply_split_body<TR, true>(a, tiles_x, tiles, nbias, ps);
+    reduce_apply_split_body<TR, true, false>(a, tiles_x, tiles, nbias, ps, MomArgs{});
 }
-
 // flag |= 1 if some element of `in` is not exactly representable in bf16, |= 2 if some element is neither 0.0 nor 1.0
 // (the caller zeroes it)
 __global__ __launch_bounds__(256) void k_bf16_exact_check(const float* __restrict__ in, int rows, int cols, int ld_in,
@@ -418,7 +289,9 @@ hipError_t launch_f32_to_bf16(const float* in, int rows, int cols, int ld_in, ui
     return hipGetLastError();
 }
 
-hipError_t launch_reduce_apply_split(const ReduceArgs& a, hipStream_t st, const PeerSrc* peer) {
+hipError_t launch_reduce_apply_split(const ReduceArgs& a, hipStream_t st, const PeerSrc* peer, const MomArgs* mom) {
+    // MOM: W updated from slabs, whole aligned velocity groups, no peer source (reduce_apply_split_body)
+    if (mom && (!a.W || !a.slab || (a.n_hid & 3) || !mom->vel_w || (peer && peer->band_rows))) return hipErrorInvalidValue;
     // the tile grid covers the padded extents of both mirrors (their zero k padding is written here)
     int r_ext = a.n_vis, c_ext = a.n_hid;
     if (a.Wb && a.ldWb > c_ext) c_ext = a.ldWb;
@@ -440,6 +313,8 @@ hipError_t launch_reduce_apply_split(const ReduceArgs& a, hipStream_t st, const 
     if (ps.band_rows) {
         if (tr == 32) hipLaunchKernelGGL(k_reduce_apply_split_peer<32>, grid, dim3(256), 0, st, a, tiles_x, tiles_x * tiles_y, nb, ps);
         else hipLaunchKernelGGL(k_reduce_apply_split_peer<16>, grid, dim3(256), 0, st, a, tiles_x, tiles_x * tiles_y, nb, ps);
+    } else if (mom) {
+        return launch_reduce_apply_split_mom(a, st, tr, tiles_x, tiles_x * tiles_y, nb, *mom);   // (kurbm_mom.hip)
     } else if (tr == 64) hipLaunchKernelGGL(k_reduce_apply_split<64>, grid, dim3(256), 0, st, a, tiles_x, tiles_x * tiles_y, nb);
     else if (tr == 32) hipLaunchKernelGGL(k_reduce_apply_split<32>, grid, dim3(256), 0, st, a, tiles_x, tiles_x * tiles_y, nb);
     else hipLaunchKernelGGL(k_reduce_apply_split<16>, grid, dim3(256), 0, st, a, tiles_x, tiles_x * tiles_y, nb);

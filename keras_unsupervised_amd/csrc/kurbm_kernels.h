@@ -96,17 +96,32 @@ struct ReduceArgs {
     size_t planeWb, planeWtb;
 };
 
+// Momentum and L2 weight decay, fused into the launches that apply an update (the MOM instantiations of k_reduce_apply,
+// k_reduce_apply_split and k_apply_delta; the ordinary ones take no such block):
+//     W:   vel = mu vel + lr (g - decay W);  W += vel          b_h, b_v:   vel = mu vel + lr g;  b += vel   (no decay on biases)
+// g = the batch SUMS the launch reduces, so `decay` is on their scale.  The velocities are dense fp32 in the packed layout of
+// delta_out ([n_vis][n_hid] without row padding | n_hid | n_vis); a variable the launch does not update (W / b_h / b_v null in its
+// ReduceArgs / ApplyArgs) has its velocity neither read nor written.
+struct MomArgs {
+    float mu, decay;
+    float* vel_w;     // row 0 = the first row of W this launch handles
+    float* vel_bh;
+    float* vel_bv;
+};
+
 // Bias partials [row tiles][columns] -> column sums (k_reduce_apply, k_reduce_apply_split, and the prologue of the statistics
 // GEMM when it reduces its own slabs): one WAVE per 8 columns, lane = 8 rg + column.  A column's rows are spread over 8 lanes
 // (row groups), each with up to 8 loads in flight per pass -- one thread per column walked 128 rows of partials in 16
 // dependent passes of ~0.6 us, the longest chain of the whole launch, and it began last.  Group sums and their total in
 // double, the total by an xor-shuffle tree ((g0 + g1) + (g2 + g3)) + ((g4 + g5) + (g6 + g7)): a fixed order, bit-reproducible,
 // no LDS and no barrier.  Callers place this work FIRST in their grid.
+// MOM (a template flag; the ordinary instantiation carries none of it): the bias velocities, vel = mu vel + lr sum; b += vel.
 constexpr int BIAS_COLS = 32;     // columns per 256-thread block (4 waves)
 __host__ __device__ static inline int bias_waves(const ReduceArgs& a) { return (a.n_hid + (a.n_vis_bias ? a.n_vis_bias : a.n_vis) + 7) / 8; }
 static inline int bias_blocks(const ReduceArgs& a) { return (bias_waves(a) + 3) / 4; }
 #if defined(__HIPCC__)
-__device__ __forceinline__ void bias_colsum_wave(const ReduceArgs& a, int group, int lane) {
+template <bool MOM>
+__device__ __forceinline__ void bias_colsum_wave_t(const ReduceArgs& a, const MomArgs& mo, int group, int lane) {
     const int cl = lane & 7, rg = lane >> 3;
     const int q = group * 8 + cl;
     const int nvb = a.n_vis_bias ? a.n_vis_bias : a.n_vis;
@@ -136,12 +151,19 @@ __device__ __forceinline__ void bias_colsum_wave(const ReduceArgs& a, int group,
         const float v = (float)u;
         if (hid) {
             if (a.delta_bh) a.delta_bh[col] = v;
-            if (a.b_h) a.b_h[col] += a.lr * v;
+            if constexpr (MOM) {
+                if (a.b_h) { const float vel = mo.mu * mo.vel_bh[col] + a.lr * v; mo.vel_bh[col] = vel; a.b_h[col] += vel; }
+            } else if (a.b_h) a.b_h[col] += a.lr * v;
         } else {
             if (a.delta_bv) a.delta_bv[col] = v;
-            if (a.b_v) a.b_v[col] += a.lr * v;
+            if constexpr (MOM) {
+                if (a.b_v) { const float vel = mo.mu * mo.vel_bv[col] + a.lr * v; mo.vel_bv[col] = vel; a.b_v[col] += vel; }
+            } else if (a.b_v) a.b_v[col] += a.lr * v;
         }
     }
+}
+__device__ __forceinline__ void bias_colsum_wave(const ReduceArgs& a, int group, int lane) {
+    bias_colsum_wave_t<false>(a, MomArgs{}, group, lane);
 }
 #endif
 
@@ -327,9 +349,14 @@ hipError_t launch_f32_to_bf16(const float* in, int rows, int cols, int ld_in, ui
 hipError_t launch_bf16_exact_check(const float* in, int rows, int cols, int ld_in, int* flag, hipStream_t st);
 hipError_t launch_gemm(int layout, int cfg, int epi, const GemmArgs& g, hipStream_t st);
 hipError_t launch_philox_uniform(float* out, int rows, int cols, int ld, const RngArgs& rng, hipStream_t st);
-hipError_t launch_reduce_apply(const ReduceArgs& a, hipStream_t st);
-hipError_t launch_reduce_apply_split(const ReduceArgs& a, hipStream_t st, const PeerSrc* peer = nullptr);
-hipError_t launch_apply_delta(const ApplyArgs& a, hipStream_t st);
+// mom (nullable): the MOM instantiation of the kernel; null launches the ordinary one
+hipError_t launch_reduce_apply(const ReduceArgs& a, hipStream_t st, const MomArgs* mom = nullptr);
+hipError_t launch_reduce_apply_split(const ReduceArgs& a, hipStream_t st, const PeerSrc* peer = nullptr, const MomArgs* mom = nullptr);
+hipError_t launch_apply_delta(const ApplyArgs& a, hipStream_t st, const MomArgs* mom = nullptr);
+// kurbm_mom.hip: the MOM kernels (geometry as their callers above computed it)
+hipError_t launch_reduce_apply_split_mom(const ReduceArgs& a, hipStream_t st, int tr, int tiles_x, int tiles, int nb, const MomArgs& mo);
+hipError_t launch_reduce_apply_mom(const ReduceArgs& a, hipStream_t st, int nb, int nb8, const MomArgs& mo);
+hipError_t launch_apply_delta_mom(const ApplyArgs& a, hipStream_t st, const MomArgs& mo);
 hipError_t launch_free_energy_finish(const FinishArgs& a, hipStream_t st);
 
 }  // namespace kurbm

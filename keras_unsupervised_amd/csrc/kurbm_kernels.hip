@@ -39,6 +39,7 @@
 
 #include "kurbm_kernels.h"
 #include "kurbm_device.h"
+#include "kurbm_reduce.h"
 
 namespace kurbm {
 
@@ -595,103 +596,11 @@ __global__ __launch_bounds__(NTHREADS) void k_gemm(GemmArgs g) {
 // The first nbias8 blocks (nbias rounded up to 8, so that the blocks behind keep their XCD) reduce the bias partials
 // (kurbm_kernels.h: bias_colsum_wave); the nblk_w blocks after them sum the split-K slabs of dW (4 columns per thread) and
 // either add lr * dW into W or store dW densely.
+// MOM (a template flag: the ordinary kernel carries none of it in its code or its argument segment): the update goes through the
+// velocity (kurbm_kernels.h: MomArgs) -- one more read-modify-write per weight group, in the pass that already touches it.
 __global__ __launch_bounds__(256) void k_reduce_apply(ReduceArgs a, int nbias, int nbias8) {
     warm_kernel_arguments<sizeof(ReduceArgs) + 8>();   // (kurbm_device.h: one wait for the argument segment, not one per use)
-    const int tid = threadIdx.x;
-    if ((int)blockIdx.x < nbias8) {
-        if ((int)blockIdx.x < nbias) bias_colsum_wave(a, blockIdx.x * 4 + (tid >> 6), tid & 63);
-        return;
-    }
-    const int blk = (int)blockIdx.x - nbias8;
-    if (blk < a.nblk_w) {
-        if (a.tile_bm > 0) {
-            // tile order: the same XCD remap as the GEMM, then (tile, part of the tile)
-            const int nwg = a.nblk_w;
-            int bid = blk;
-            const int xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
-            bid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
-            const int tile = bid / a.parts, part = bid - tile * a.parts;
-            const int bm = a.m_fastest ? tile % a.grid_m : tile / a.grid_n;
-            const int bn = a.m_fastest ? tile / a.grid_m : tile - bm * a.grid_n;
-            const int g4 = a.tile_bn / 4;
-            const int rows_pp = (a.tile_bm + a.parts - 1) / a.parts;
-            // one block = rows_pp x tile_bn floats; lanes walk the float4 groups of a row
-            for (int e = tid; e < rows_pp * g4; e += 256) {
-                const int r = part * rows_pp + e / g4;
-                const int ii = bm * a.tile_bm + r, jj = bn * a.tile_bn + 4 * (e % g4);
-                if (r >= a.tile_bm || ii >= a.n_vis || jj >= a.n_hid) continue;
-                const float* sp = a.slab + (size_t)ii * a.ld_slab + jj;
-                f32x4 s = {0.f, 0.f, 0.f, 0.f};
-                int zz = 0;
-                for (; zz + 4 <= a.nslab; zz += 4) {
-                    const f32x4 v0 = *reinterpret_cast<const f32x4*>(sp + (size_t)(zz + 0) * a.slab_stride);
-                    const f32x4 v1 = *reinterpret_cast<const f32x4*>(sp + (size_t)(zz + 1) * a.slab_stride);
-                    const f32x4 v2 = *reinterpret_cast<const f32x4*>(sp + (size_t)(zz + 2) * a.slab_stride);
-                    const f32x4 v3 = *reinterpret_cast<const f32x4*>(sp + (size_t)(zz + 3) * a.slab_stride);
-                    s += v0; s += v1; s += v2; s += v3;
-                }
-                for (; zz < a.nslab; ++zz) s += *reinterpret_cast<const f32x4*>(sp + (size_t)zz * a.slab_stride);
-                if (jj + 3 < a.n_hid) {
-                    if (a.W) {
-                        f32x4* w = reinterpret_cast<f32x4*>(a.W + (size_t)ii * a.ldw + jj);
-                        *w = *w + s * a.lr;
-                    }
-                    if (a.delta_w) {
-                        float* d = a.delta_w + (size_t)ii * a.n_hid + jj;
-                        if ((a.n_hid & 3) == 0) *reinterpret_cast<f32x4*>(d) = s;
-                        else { d[0] = s.x; d[1] = s.y; d[2] = s.z; d[3] = s.w; }
-                    }
-                } else {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        if (jj + u < a.n_hid) {
-                            if (a.delta_w) a.delta_w[(size_t)ii * a.n_hid + jj + u] = s[u];
-                            if (a.W) a.W[(size_t)ii * a.ldw + jj + u] += a.lr * s[u];
-                        }
-                }
-            }
-            return;
-        }
-    }
-    if (blk < a.nblk_w) {   // row order (no tile geometry given)
-        const int groups = a.ld_slab / 4;  // float4 groups per row
-        const long long q = (long long)blk * 256 + tid;
-        if (q >= (long long)a.n_vis * groups) return;
-        const int i = (int)(q / groups), j0 = (int)(q - (long long)i * groups) * 4;
-        // slabs are summed in index order (bit-reproducible); four loads in flight per lane
-        const float* sp = a.slab + (size_t)i * a.ld_slab + j0;
-        f32x4 s = {0.f, 0.f, 0.f, 0.f};
-        int zz = 0;
-        for (; zz + 4 <= a.nslab; zz += 4) {
-            const f32x4 v0 = *reinterpret_cast<const f32x4*>(sp + (size_t)(zz + 0) * a.slab_stride);
-            const f32x4 v1 = *reinterpret_cast<const f32x4*>(sp + (size_t)(zz + 1) * a.slab_stride);
-            const f32x4 v2 = *reinterpret_cast<const f32x4*>(sp + (size_t)(zz + 2) * a.slab_stride);
-            const f32x4 v3 = *reinterpret_cast<const f32x4*>(sp + (size_t)(zz + 3) * a.slab_stride);
-            s += v0; s += v1; s += v2; s += v3;
-        }
-        for (; zz < a.nslab; ++zz) s += *reinterpret_cast<const f32x4*>(sp + (size_t)zz * a.slab_stride);
-        if (j0 + 3 < a.n_hid) {   // whole 16-B group inside the matrix: vector read-modify-write
-            if (a.W) {
-                f32x4* w = reinterpret_cast<f32x4*>(a.W + (size_t)i * a.ldw + j0);
-                *w = *w + s * a.lr;
-            }
-            if (a.delta_w) {
-                float* d = a.delta_w + (size_t)i * a.n_hid + j0;
-                if ((a.n_hid & 3) == 0) *reinterpret_cast<f32x4*>(d) = s;
-                else { d[0] = s.x; d[1] = s.y; d[2] = s.z; d[3] = s.w; }
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int j = j0 + e;
-                if (j < a.n_hid) {
-                    if (a.delta_w) a.delta_w[(size_t)i * a.n_hid + j] = s[e];
-                    if (a.W) a.W[(size_t)i * a.ldw + j] += a.lr * s[e];
-                }
-            }
-        }
-        return;
-    }
+    reduce_apply_body<false>(a, MomArgs{}, nbias, nbias8);
 }
 
 // params += lr * delta for a packed [V*H | H | V] delta
@@ -709,7 +618,6 @@ __global__ __launch_bounds__(256) void k_apply_delta(ApplyArgs a) {
         if (a.b_v) a.b_v[q - nw - a.n_hid] += a.lr * a.delta[q];
     }
 }
-
 // F[row] = -( v[row].b_v + sum over column tiles of the softplus row partials )
 __global__ __launch_bounds__(256) void k_free_energy_finish(FinishArgs a) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -873,14 +781,16 @@ hipError_t launch_philox_uniform(float* out, int rows, int cols, int ld, const R
     return hipGetLastError();
 }
 
-hipError_t launch_reduce_apply(const ReduceArgs& a, hipStream_t st) {
+hipError_t launch_reduce_apply(const ReduceArgs& a, hipStream_t st, const MomArgs* mom) {
     const int nb = bias_blocks(a), nb8 = (nb + 7) / 8 * 8;
+    if (mom) return launch_reduce_apply_mom(a, st, nb, nb8, *mom);   // (kurbm_mom.hip)
     hipLaunchKernelGGL(k_reduce_apply, dim3(a.nblk_w + nb8), dim3(256), 0, st, a, nb, nb8);
     return hipGetLastError();
 }
 
-hipError_t launch_apply_delta(const ApplyArgs& a, hipStream_t st) {
+hipError_t launch_apply_delta(const ApplyArgs& a, hipStream_t st, const MomArgs* mom) {
     const long long n = (long long)a.n_vis * a.n_hid + a.n_hid + a.n_vis;
+    if (mom) return launch_apply_delta_mom(a, st, *mom);   // (kurbm_mom.hip)
     hipLaunchKernelGGL(k_apply_delta, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
     return hipGetLastError();
 }

@@ -5,12 +5,15 @@ The reference has no EBM-specific format: the example saves the whole Keras mode
 weights.  Both lose part of an RBM: `get_config` omits `mode` (reference ku/ebm/rbm.py:236-242) and
 `visible_bias` is a bare variable outside `get_weights()` (rbm.py:38-40).  Here a checkpoint is
 
-    <stem>.json          get_config() (hps, output_dim, name, mode, seed, update_mode, cd_k, persistent)
-                         + input_dim + the RNG counters, so a reloaded RBM continues the same stream
+    <stem>.json          get_config() (hps, output_dim, name, mode, seed, update_mode, cd_k, persistent, momentum, weight_decay)
+                         + input_dim + the RNG counters, so a reloaded RBM continues the same stream, + the epochs trained
+                         (the index into a momentum schedule)
     <stem>.safetensors   rbm_weight [n_vis, n_hid], rbm_hidden_bias [n_hid], rbm_visible_bias [n_vis], fp32;
                          with persistent=True also v_chain [batch_size, n_vis], the fantasy particles, so that a
                          reloaded RBM continues the chain it was saved with (data parallel: assembled over the ranks,
-                         each of which owns a band of its rows; save_rbm is then a collective call, rank 0 writes)
+                         each of which owns a band of its rows; save_rbm is then a collective call, rank 0 writes);
+                         once a momentum step has run also velocity_weight [n_vis, n_hid], velocity_hidden_bias [n_hid],
+                         velocity_visible_bias [n_vis] (a checkpoint without them loads with a zero velocity)
 
 and a DBN checkpoint is a JSON list of layer stems.
 """
@@ -29,9 +32,11 @@ def save_rbm(rbm, stem):
         raise ValueError("cannot checkpoint an RBM that has not been built")
     W, b_h, b_v = rbm.get_weights()
     cfg = {k: v for k, v in rbm.get_config().items() if k in
-           ("hps", "output_dim", "name", "mode", "seed", "update_mode", "cd_k", "persistent", "compute_dtype")}
+           ("hps", "output_dim", "name", "mode", "seed", "update_mode", "cd_k", "persistent", "compute_dtype", "momentum",
+            "weight_decay")}
     meta = {"format": "kurbm-rbm", "version": FORMAT_VERSION, "config": cfg, "input_dim": int(W.shape[0]),
-            "update_count": int(rbm._update_count), "call_count": int(rbm._call_count)}
+            "update_count": int(rbm._update_count), "call_count": int(rbm._call_count),
+            "epochs_done": int(getattr(rbm, "_epochs_done", 0))}
     os.makedirs(os.path.dirname(os.path.abspath(stem)), exist_ok=True)
     tensors = {"rbm_weight": np.ascontiguousarray(W, dtype=np.float32),
                "rbm_hidden_bias": np.ascontiguousarray(b_h, dtype=np.float32),
@@ -40,6 +45,10 @@ def save_rbm(rbm, stem):
         # data parallel: every rank advances only its own rows of the chain, so the chain is assembled over the ranks first
         # (RBM.full_chain: a collective -- every rank calls save_rbm; rank 0 writes the files)
         tensors["v_chain"] = np.ascontiguousarray(rbm.full_chain(), dtype=np.float32)
+    vel = rbm._dev.get_velocity() if hasattr(rbm._dev, "get_velocity") else None
+    if vel is not None:     # (identical on every rank of a data-parallel run: the summed delta is)
+        for name, x in zip(("velocity_weight", "velocity_hidden_bias", "velocity_visible_bias"), vel):
+            tensors[name] = np.ascontiguousarray(x, dtype=np.float32)
     from . import dp
     if dp.world()[0] != 0:
         return stem + ".json", stem + ".safetensors"
@@ -67,6 +76,12 @@ def load_rbm(stem, device=None):
     rbm.build((None, meta["input_dim"]))
     rbm._update_count = int(meta.get("update_count", 0))
     rbm._call_count = int(meta.get("call_count", 0))
+    rbm._epochs_done = int(meta.get("epochs_done", 0))
+    if "velocity_weight" in t:
+        if t["velocity_weight"].shape != W.shape or t["velocity_hidden_bias"].shape != b_h.shape \
+                or t["velocity_visible_bias"].shape != b_v.shape:
+            raise ValueError("checkpoint velocity tensors do not match its weights")
+        rbm._dev.set_velocity(t["velocity_weight"], t["velocity_hidden_bias"], t["velocity_visible_bias"])
     if "v_chain" in t:
         from .engine import DeviceMatrix, device_guard
         # (fit() reads and rewrites batch_size rows of the chain in place: any other row count is refused here, not there)

@@ -11,7 +11,7 @@ import torch
 
 from .. import _lib
 from .._lib import (ACT_LINEAR, ACT_RELU, ACT_SIGMOID, NOISE_BERNOULLI, NOISE_GAUSSIAN, NOISE_NONE,
-                    WHICH_ALL, CdOpts, Context, Params, Rng, check)
+                    WHICH_ALL, CdOpts, Context, Momentum, Params, Rng, check)
 
 MODE_VISIBLE_BERNOULLI = 0
 MODE_VISIBLE_GAUSSIAN = 1
@@ -152,6 +152,7 @@ class DeviceRBM:
         # 3 = exact hi/mid/lo split (compute 'x3');  [tensor, stale]
         self._mirrors = {}
         self._ws_b = {}
+        self.velocity = None   # packed [V*H | H | V] fp32 velocity of the momentum steps, allocated (zero) on first use
 
     # -- plumbing -------------------------------------------------------------------
     def _stream(self):
@@ -171,6 +172,36 @@ class DeviceRBM:
             n = self.n_vis * self.n_hid + self.n_hid + self.n_vis
             self.delta = torch.zeros(n, dtype=torch.float32, device=self.device)
         return self.delta
+
+    # -- momentum / weight decay (include/kurbm.h: kurbm_momentum) -------------------------------
+    def velocity_buffer(self):
+        if self.velocity is None:
+            n = self.n_vis * self.n_hid + self.n_hid + self.n_vis
+            with torch.cuda.device(self.device):
+                self.velocity = torch.zeros(n, dtype=torch.float32, device=self.device)
+        return self.velocity
+
+    def _mom(self, momentum):
+        """The kurbm_momentum block of a `momentum=` keyword: (mu, weight_decay), or mu alone.  The rule, all fp32:
+        vel <- mu vel + lr (g - weight_decay W); W <- W + vel (biases: no decay), g = the batch SUMS -- so weight_decay is on
+        the scale of those sums (lr multiplies sums: rbm.py:128), not of a per-row mean."""
+        mu, decay = momentum if isinstance(momentum, (tuple, list)) else (momentum, 0.0)
+        return Momentum(float(mu), float(decay), self.velocity_buffer().data_ptr())
+
+    def get_velocity(self):
+        """(vel_W [n_vis, n_hid], vel_b_h, vel_b_v) as host arrays, or None when no momentum step has run (or set_velocity)."""
+        if self.velocity is None:
+            return None
+        v, nw = self.velocity.cpu().numpy(), self.n_vis * self.n_hid
+        return v[:nw].reshape(self.n_vis, self.n_hid).copy(), v[nw:nw + self.n_hid].copy(), v[nw + self.n_hid:].copy()
+
+    def set_velocity(self, W=None, b_h=None, b_v=None):
+        buf, nw = self.velocity_buffer(), self.n_vis * self.n_hid
+        for x, lo, n in ((W, 0, nw), (b_h, nw, self.n_hid), (b_v, nw + self.n_hid, self.n_vis)):
+            if x is not None:
+                x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+                assert x.size == n
+                buf[lo:lo + n].copy_(torch.from_numpy(x))
 
     # -- bf16 mirrors (fp32 master weights stay authoritative) --------------------------------
     def _weights_written(self, kept=None):
@@ -303,12 +334,18 @@ class DeviceRBM:
 
     def cd_step(self, v, rows, row_start, lr, seed, step, k=1, mode=MODE_VISIBLE_BERNOULLI, chain=0,
                 which=WHICH_ALL, apply=True, emit_delta=False, v_chain=None, row0=0, v_chain_row=0, bf16=False,
-                compute=None, planes=None):
+                compute=None, planes=None, momentum=None):
         """One CD-k update on rows [row_start, row_start+rows) of DeviceMatrix v.
 
         compute: 'fp32' (fp32 MFMA), 'x3' (fp32 values as exact bf16 triples on the bf16 MFMA),
-        'bf16' (operands rounded to bf16).  planes: ResidentPlanes holding these rows (x3: no per-step conversion)."""
+        'bf16' (operands rounded to bf16).  planes: ResidentPlanes holding these rows (x3: no per-step conversion).
+        momentum: None (the reference's bare rule, on the plain entry points) or (mu, weight_decay) -- the update goes through this
+        engine's velocity inside the same launch (the *_mom entry points; see _mom for the rule and the scale of weight_decay).
+        The one-launch 'small' step has no momentum."""
         compute = compute or ("bf16" if bf16 else "fp32")
+        if momentum is not None and compute == "small":
+            raise ValueError("the one-launch 'small' step has no momentum: use 'fp32', 'x3' or 'bf16'")
+        # (the plain calls stay as they were, argument for argument: this is the step loop's host path)
         with torch.cuda.device(self.device):
             opts = CdOpts(int(k), int(mode), float(lr), 1 if apply else 0,
                           self.delta_buffer().data_ptr() if emit_delta else None,
@@ -316,9 +353,14 @@ class DeviceRBM:
                           int(seed), int(row0), int(step) & 0xFFFFFFFF, int(chain))
             if compute == "bf16":
                 mir, ws = self.mirror(1), self.workspace_bf16(rows, k)
-                check(self.lib.kurbm_cd_step_bf16(self.ctx.handle, C.byref(self.params), mir.data_ptr(), mir.numel(),
-                                                  v.ptr(row_start), rows, v.ld, C.byref(opts), int(which),
-                                                  ws.data_ptr(), ws.numel(), self._stream()))
+                if momentum is None:
+                    check(self.lib.kurbm_cd_step_bf16(self.ctx.handle, C.byref(self.params), mir.data_ptr(), mir.numel(),
+                                                      v.ptr(row_start), rows, v.ld, C.byref(opts), int(which),
+                                                      ws.data_ptr(), ws.numel(), self._stream()))
+                else:
+                    check(self.lib.kurbm_cd_step_bf16_mom(self.ctx.handle, C.byref(self.params), mir.data_ptr(), mir.numel(),
+                                                          v.ptr(row_start), rows, v.ld, C.byref(opts), int(which),
+                                                          ws.data_ptr(), ws.numel(), self._stream(), C.byref(self._mom(momentum))))
                 if apply and (which & 1):
                     self._weights_written(kept=1)
             elif compute == "x3":
@@ -326,15 +368,25 @@ class DeviceRBM:
                 mir, ws = self.mirror(3), self.workspace_bf16(rows, k, 3, vp)
                 if planes is not None:
                     opts.v_planes = planes.ptr(v, row_start, rows, vp)
-                check(self.lib.kurbm_cd_step_x3(self.ctx.handle, C.byref(self.params), mir.data_ptr(), mir.numel(),
-                                                v.ptr(row_start), vp, rows, v.ld, C.byref(opts), int(which),
-                                                ws.data_ptr(), ws.numel(), self._stream()))
+                if momentum is None:
+                    check(self.lib.kurbm_cd_step_x3(self.ctx.handle, C.byref(self.params), mir.data_ptr(), mir.numel(),
+                                                    v.ptr(row_start), vp, rows, v.ld, C.byref(opts), int(which),
+                                                    ws.data_ptr(), ws.numel(), self._stream()))
+                else:
+                    check(self.lib.kurbm_cd_step_x3_mom(self.ctx.handle, C.byref(self.params), mir.data_ptr(), mir.numel(),
+                                                        v.ptr(row_start), vp, rows, v.ld, C.byref(opts), int(which),
+                                                        ws.data_ptr(), ws.numel(), self._stream(), C.byref(self._mom(momentum))))
                 if apply and (which & 1):
                     self._weights_written(kept=3)
             elif compute == "fp32":
                 ws = self.workspace(rows, k)
-                check(self.lib.kurbm_cd_step(self.ctx.handle, C.byref(self.params), v.ptr(row_start), rows, v.ld,
-                                             C.byref(opts), int(which), ws.data_ptr(), ws.numel(), self._stream()))
+                if momentum is None:
+                    check(self.lib.kurbm_cd_step(self.ctx.handle, C.byref(self.params), v.ptr(row_start), rows, v.ld,
+                                                 C.byref(opts), int(which), ws.data_ptr(), ws.numel(), self._stream()))
+                else:
+                    check(self.lib.kurbm_cd_step_mom(self.ctx.handle, C.byref(self.params), v.ptr(row_start), rows, v.ld,
+                                                     C.byref(opts), int(which), ws.data_ptr(), ws.numel(), self._stream(),
+                                                     C.byref(self._mom(momentum))))
                 if apply and (which & 1):
                     self._weights_written()
             elif compute == "small":
@@ -349,13 +401,25 @@ class DeviceRBM:
         self._chain_written(v_chain, mode)
 
     def cd_step_dp(self, comm, v, rows, row_start, lr, seed, step, k=1, mode=MODE_VISIBLE_BERNOULLI, chain=0, row0=0,
-                   v_chain=None, v_chain_row=0, compute="x3", n_chunks=0, planes=None):
+                   v_chain=None, v_chain_row=0, compute="x3", n_chunks=0, planes=None, momentum=None):
         """One data-parallel CD-k update: this rank's chain on rows [row_start, +rows) of v (`row0` = their index in
         the global batch), the packed sums all-reduced over `comm` (dp.Comm), the summed update applied.  rows may be 0
         (a rank without rows of a remainder batch still joins the all-reduce).  On the x3 and rounded-bf16 paths all of it
         is ONE library call (kurbm_cd_step_x3_dp / _bf16_dp): one all-reduce of the packed sums on the launch stream (n_chunks > 1
         or KURBM_DP_CHUNKS > 1 opts into row ranges of dW, range i all-reduced + applied on the library's comm stream under the
-        statistics GEMM of range i + 1); the fp32-MFMA path runs emit -> kurbm_allreduce_sum_f32 -> apply."""
+        statistics GEMM of range i + 1); the fp32-MFMA path runs emit -> kurbm_allreduce_sum_f32 -> apply.
+        momentum (see cd_step): every exchange then runs that generic sequence, its apply through the velocity
+        (kurbm_apply_delta_mom / kurbm_x3_apply_delta_mom); the summed delta is the same on all ranks, so are the velocities."""
+        if momentum is not None:
+            delta = self.delta_buffer()
+            if rows > 0:
+                self.cd_step(v, rows, row_start, lr, seed, step, k=k, mode=mode, chain=chain, apply=False, emit_delta=True,
+                             v_chain=v_chain, row0=row0, v_chain_row=v_chain_row, compute=compute, planes=planes)
+            else:
+                delta.zero_()
+            comm.allreduce_sum_(delta)
+            self.apply_delta(lr, compute=compute, momentum=momentum)
+            return
         if hasattr(comm, "capacity") and compute == "x3":
             # the peer exchange (dp.PeerExchange): chain, statistics, two-shot exchange with the apply fused into its second shot
             with torch.cuda.device(self.device):
@@ -422,8 +486,15 @@ class DeviceRBM:
                 self._weights_written(kept=3)
 
     def cd_epoch(self, v, n_rows, batch_size, lr, seed, step0, k=1, mode=MODE_VISIBLE_BERNOULLI, v_chain=None,
-                 compute="fp32", row_start=0, planes=None):
-        """All batches of rows [row_start, row_start + n_rows) in ONE library call (fused updates, no score); returns #steps."""
+                 compute="fp32", row_start=0, planes=None, momentum=None):
+        """All batches of rows [row_start, row_start + n_rows) in ONE library call (fused updates, no score); returns #steps.
+        momentum (see cd_step): one (mu, weight_decay) for the whole call."""
+        if momentum is not None and compute == "small":
+            raise ValueError("the one-launch 'small' step has no momentum: use 'fp32' or 'x3'")
+        mom = ()
+        if momentum is not None:
+            with torch.cuda.device(self.device):
+                mom = (C.byref(self._mom(momentum)),)
         if compute == "x3":
             with torch.cuda.device(self.device):
                 vp = self._x3_pieces(v, v_chain, mode)
@@ -433,9 +504,10 @@ class DeviceRBM:
                               int(seed), 0, int(step0) & 0xFFFFFFFF, 0)
                 if planes is not None and planes.v is v and planes.v_pieces == vp and planes.uniform(row_start, n_rows, batch_size):
                     opts.v_planes, opts.v_planes_stride = planes.buf.data_ptr(), planes.stride
-                n = self.lib.kurbm_cd_epoch_x3(self.ctx.handle, C.byref(self.params), mir.data_ptr(), mir.numel(), v.ptr(row_start), vp,
-                                               int(n_rows), v.ld, int(batch_size), C.byref(opts), ws.data_ptr(), ws.numel(),
-                                               self._stream())
+                fn = self.lib.kurbm_cd_epoch_x3_mom if mom else self.lib.kurbm_cd_epoch_x3
+                n = fn(self.ctx.handle, C.byref(self.params), mir.data_ptr(), mir.numel(), v.ptr(row_start), vp,
+                       int(n_rows), v.ld, int(batch_size), C.byref(opts), ws.data_ptr(), ws.numel(),
+                       self._stream(), *mom)
                 if n < 0:
                     check(n)
             self._weights_written(kept=3)
@@ -445,9 +517,9 @@ class DeviceRBM:
             ws = self.workspace(min(batch_size, max(n_rows, 1)), k)
             opts = CdOpts(int(k), int(mode), float(lr), 1, None, v_chain.ptr() if v_chain is not None else None,
                           int(seed), 0, int(step0) & 0xFFFFFFFF, 0)
-            fn = self.lib.kurbm_cd_epoch_small if compute == "small" else self.lib.kurbm_cd_epoch
+            fn = self.lib.kurbm_cd_epoch_small if compute == "small" else (self.lib.kurbm_cd_epoch_mom if mom else self.lib.kurbm_cd_epoch)
             n = fn(self.ctx.handle, C.byref(self.params), v.ptr(row_start), int(n_rows), v.ld,
-                                        int(batch_size), C.byref(opts), ws.data_ptr(), ws.numel(), self._stream())
+                                        int(batch_size), C.byref(opts), ws.data_ptr(), ws.numel(), self._stream(), *mom)
             if n < 0:
                 check(n)
         self._weights_written()
@@ -499,20 +571,23 @@ class DeviceRBM:
                 out["sample"].bf16_exact = out["sample"].binary = False
         return out
 
-    def apply_delta(self, lr, which=WHICH_ALL, delta=None, compute=None):
+    def apply_delta(self, lr, which=WHICH_ALL, delta=None, compute=None, momentum=None):
         """W, b_h, b_v += lr * delta (the all-reduced packed sums).  compute='x3' also rewrites the weight-piece
-        mirror in the same launch."""
+        mirror in the same launch.  momentum (see cd_step): the same update through the velocity."""
         delta = self.delta_buffer() if delta is None else delta
         with torch.cuda.device(self.device):
+            mom = (C.byref(self._mom(momentum)),) if momentum is not None else ()
             if compute == "x3" and 3 in self._mirrors:
                 mir = self._mirrors[3][0]
-                check(self.lib.kurbm_x3_apply_delta(self.ctx.handle, C.byref(self.params), mir.data_ptr(), mir.numel(),
-                                                    delta.data_ptr(), float(lr), int(which), self._stream()))
+                fn = self.lib.kurbm_x3_apply_delta_mom if mom else self.lib.kurbm_x3_apply_delta
+                check(fn(self.ctx.handle, C.byref(self.params), mir.data_ptr(), mir.numel(),
+                         delta.data_ptr(), float(lr), int(which), self._stream(), *mom))
                 self._weights_written(kept=3)
                 self._mirrors[3][1] = False
                 return
-            check(self.lib.kurbm_apply_delta(self.ctx.handle, C.byref(self.params), delta.data_ptr(), float(lr),
-                                             int(which), self._stream()))
+            fn = self.lib.kurbm_apply_delta_mom if mom else self.lib.kurbm_apply_delta
+            check(fn(self.ctx.handle, C.byref(self.params), delta.data_ptr(), float(lr),
+                     int(which), self._stream(), *mom))
         self._weights_written()
 
     def free_energy(self, v, rows, row_start=0, compute=None):

@@ -16,7 +16,8 @@ shape follows the probabilities, remainder-batch shape, list returns of K.functi
 Extensions, all off by default or reference-preserving: ``update_mode='fused'`` (one Gibbs chain
 feeds all three updates; ``'reference_sequential'`` replays the reference's three chains),
 ``cd_k``, ``persistent`` chains, ``seed``, data-parallel training when torch.distributed is
-initialised, ``verbose=0`` to skip the score passes.
+initialised, ``verbose=0`` to skip the score passes, ``momentum`` / ``weight_decay`` (both 0 by
+default: the reference's bare rule on the same kernels).
 """
 import collections
 import time
@@ -92,13 +93,29 @@ class RBM(object):
             raise ValueError("update_mode must be one of %s" % (_UPDATE_MODES,))
         self.cd_k = int(opt("cd_k", 1))
         self.persistent = bool(opt("persistent", False))
+        # momentum and L2 weight decay, fused into the launch that applies the update (extension; 0 / 0 = the reference's bare rule,
+        # through the same entry points as before):  vel <- mu vel + lr (g - weight_decay W); W <- W + vel (biases: no decay).
+        # g = the batch SUMS, as lr multiplies sums (rbm.py:128) -- so weight_decay is on the scale of those sums: a mean-gradient
+        # recipe's lambda (Hinton's guide: ~1e-4) times the batch size.  It is not rescaled by the row count (a remainder batch,
+        # a data-parallel shard: the apply sees only the sum).  momentum: a float, or a sequence indexed by epoch whose last value
+        # holds for every later epoch -- [0.5] * 5 + [0.9] is Hinton's schedule.
+        mu = opt("momentum", 0.0)
+        self.momentum = [float(m) for m in mu] if isinstance(mu, (list, tuple)) else float(mu)
+        self.weight_decay = float(opt("weight_decay", 0.0))
+        if isinstance(self.momentum, list) and not self.momentum:
+            raise ValueError("momentum: an empty schedule")
+        if any(not 0.0 <= m < 1.0 for m in (self.momentum if isinstance(self.momentum, list) else [self.momentum])):
+            raise ValueError("momentum must be in [0, 1)")
+        if not self.weight_decay >= 0.0:
+            raise ValueError("weight_decay must be >= 0")
         # how the matrix products of fit() run (extension; storage, accumulation and results are fp32 in all):
         #   'fp32'  fp32 MFMA               'x3'  fp32 values as exact bf16 triples on the bf16 MFMA
         #   'bf16'  operands ROUNDED to bf16 (reduced precision, BASELINE.json config 5)
         #   'small' the whole CD-1 step in ONE launch (kurbm_cd_step_small; fp32 MFMA): the reference example's own sizes
         #   'auto'  (default) 'x3' at batch sizes >= 256 (tools/bench_fit.py, 784 x 1024, us per step fp32 / x3,
         #           end of round 3: batch 256 95 / 87, 512 102 / 87, 1024 122 / 95, 2048 194 / 105, 4096 341 / 129); below that
-        #           'small' where it applies (CD-1 from the data, one GPU), else 'fp32' 
+        #           'small' where it applies (CD-1 from the data, one GPU, no momentum and no weight decay: the one-launch kernel
+        #           has neither, so with either term set 'auto' and 'small' take the five-launch paths, as they do for cd_k > 1), else 'fp32' 
         self.compute_dtype = str(opt("compute_dtype", "auto"))
         if self.compute_dtype not in ("fp32", "x3", "bf16", "small", "auto"):
             raise ValueError("compute_dtype must be 'fp32', 'x3', 'bf16', 'small' or 'auto'")
@@ -114,6 +131,8 @@ class RBM(object):
         self._call_count = 0           # `step` of the RNG contract for transform / inv_transform / call
         self._v_chain = None           # persistent fantasy particles
         self._planes = None            # engine.ResidentPlanes of the data matrix during an x3 fit()
+        self._epochs_done = 0          # epochs this object has trained: the index into a momentum schedule
+        self._mom_kw = {}              # the `momentum=` keyword of this epoch's engine calls; empty with both terms 0
         self.last_scores = []
 
     # ------------------------------------------------------------------ build ----------
@@ -349,10 +368,14 @@ class RBM(object):
         for epoch in range(int(self.hps["epochs"])):                              # rbm.py:113
             if verbose == 1:
                 print(epoch + 1, "/", self.hps["epochs"], " epochs", end="\r")   # rbm.py:115
+            # (the keyword is passed only when one of the two terms is set: the default path makes the plain calls, and engine
+            # doubles without the keyword keep working)
+            self._mom_kw = {"momentum": (self.momentum_at(self._epochs_done), self.weight_decay)} if self._has_momentum() else {}
+            self._epochs_done += 1
             if whole_epochs:
                 self._update_count += d.cd_epoch(Vd, n, bs, lr, self.seed, self._update_count, k=self.cd_k,
                                                  mode=self.mode, v_chain=self._v_chain if self.persistent else None,
-                                                 compute=self._compute(), planes=planes)
+                                                 compute=self._compute(), planes=planes, **self._mom_kw)
                 continue
             if scored_epochs:
                 # small RBMs with the reference's default verbose = 1: the epoch's updates AND scores are queued by one library
@@ -389,6 +412,15 @@ class RBM(object):
         d.check_status()                  # fit() ends with one status read: no later call trains on from a skipped update
         return None
 
+    def momentum_at(self, epoch):
+        """mu of epoch `epoch` (0-based, counted over every fit() of this object): a schedule's last value holds from its end on."""
+        m = self.momentum
+        return m[min(int(epoch), len(m) - 1)] if isinstance(m, list) else m
+
+    def _has_momentum(self):
+        m = self.momentum
+        return self.weight_decay != 0.0 or (any(x != 0.0 for x in m) if isinstance(m, list) else m != 0.0)
+
     def _compute(self):
         """The compute path of this fit.  'auto' reads tools/small_crossover.py's tables (784 visible units, one MI355X;
         profiles/r04_e_compute_path_crossover.txt):
@@ -398,7 +430,7 @@ class RBM(object):
         * real-valued data or Gaussian visibles (three pieces per value, seven launches): x3 from rows x n_vis x n_hid >= 6e8 on
           (batch 1024 at 784 x 1024, 1536 at 784 x 512), the fp32-MFMA kernels below."""
         c = self.compute_dtype
-        small_ok = self.cd_k == 1 and not self.persistent and dp.world()[1] == 1
+        small_ok = self.cd_k == 1 and not self.persistent and dp.world()[1] == 1 and not self._has_momentum()
         if c == "auto":
             b, h = int(self.hps["batch_size"]), int(self.output_dim)
             if small_ok and ((b <= 128 and h <= 1024) or (b <= 256 and h <= 512) or (b <= 384 and h <= 256) or (b <= 512 and h <= 128)):
@@ -407,20 +439,21 @@ class RBM(object):
             n_vis = self._dev.n_vis if self._dev is not None else 784
             return "x3" if (not real or float(b) * n_vis * h >= 6e8) else "fp32"
         if c == "small" and not small_ok:
-            return "fp32"     # the one-launch step is CD-1 from the data on one GPU; everything else runs the five-launch path
+            return "fp32"     # the one-launch step is CD-1 from the data on one GPU, bare rule; everything else runs the five-launch path
         return c
 
     def _update_local(self, Vd, lo, rows, lr, step):
         d = self._dev
         if self.update_mode == "fused":
             d.cd_step(Vd, rows, lo, lr, self.seed, step, k=self.cd_k, mode=self.mode, chain=CHAIN_W,
-                      v_chain=self._v_chain if self.persistent else None, compute=self._compute(), planes=self._planes)
+                      v_chain=self._v_chain if self.persistent else None, compute=self._compute(), planes=self._planes,
+                      **self._mom_kw)
         else:
             # the reference's three K.function calls: each its own chain, each seeing the variables
             # the previous call already updated (rbm.py:214-216)
             for chain, which in ((CHAIN_W, _lib.WHICH_W), (CHAIN_BH, _lib.WHICH_BH), (CHAIN_BV, _lib.WHICH_BV)):
                 d.cd_step(Vd, rows, lo, lr, self.seed, step, k=1, mode=self.mode, chain=chain, which=which,
-                          compute=self._compute(), planes=self._planes)
+                          compute=self._compute(), planes=self._planes, **self._mom_kw)
 
     def _update_data_parallel(self, Vd, lo, rows, lr, step, rank, world):
         """Each rank: the chain on its rows of the batch -> packed sums -> sum all-reduce (RCCL, inside libkurbm.so) ->
@@ -431,7 +464,7 @@ class RBM(object):
         s_lo, s_hi = self._shard(rows, rank, world)
         d.cd_step_dp(dp.get_exchange(d.device, d.n_vis, d.n_hid), Vd, s_hi - s_lo, lo + s_lo, lr, self.seed, step, k=self.cd_k, mode=self.mode,
                      chain=CHAIN_W, row0=s_lo, v_chain=self._v_chain if self.persistent else None, v_chain_row=s_lo,
-                     compute=self._compute(), planes=self._planes)
+                     compute=self._compute(), planes=self._planes, **self._mom_kw)
 
     def full_chain(self):
         """The persistent chain as ONE host array [batch_size, n_vis], or None.  Under data parallelism rank r advances
@@ -461,7 +494,9 @@ class RBM(object):
         extension knobs, so that RBM(**config) rebuilds the same layer."""
         config = {"hps": self.hps, "output_dim": self.output_dim, "name": self.name, "mode": self.mode,
                   "seed": self.seed, "update_mode": self.update_mode, "cd_k": self.cd_k,
-                  "persistent": self.persistent, "compute_dtype": self.compute_dtype}
+                  "persistent": self.persistent, "compute_dtype": self.compute_dtype,
+                  "momentum": list(self.momentum) if isinstance(self.momentum, list) else self.momentum,
+                  "weight_decay": self.weight_decay}
         return dict(list(self._kwargs.items()) + list(config.items()))
 
 
