@@ -15,7 +15,9 @@
  *     synchronises with the host;
  *   - matrices are row-major fp32 [rows, ld]; ld is in floats, ld % 4 == 0, ld >= columns;
  *     base addresses are 16-byte aligned.  Columns [cols, ld) are padding: inputs may hold
- *     anything there, outputs are left untouched there;
+ *     anything there, outputs are left untouched there.  These promises -- nothing written outside a caller's buffer, padding
+ *     neither written nor let into a result, a buffer below its size query refused before anything is enqueued -- are tested:
+ *     tests/test_gpu_guard_bands.py runs every entry point on guarded, NaN-padded, wide-ld buffers (tests/guarded.py);
  *   - `stream` is a hipStream_t passed as void* (0 = the null stream);
  *   - return value: 0 = KURBM_OK, < 0 = error; kurbm_last_error() returns a thread-local
  *     message for the last failing call on this thread;
@@ -155,7 +157,12 @@ int kurbm_half_step_hv_dbg(kurbm_ctx* ctx, const kurbm_params* p, const float* h
                            int act, int noise, const kurbm_rng* rng, float* out_sample,
                            float* out_prob, float* out_u, int ldv, kurbm_stream_t stream);
 
-/* Bytes of scratch kurbm_cd_step / kurbm_free_energy need for batches of <= rows. */
+/* Bytes of scratch the fp32 entry points (kurbm_cd_step, kurbm_cd_epoch, kurbm_free_energy, kurbm_outer_delta, the small path)
+ * need for batches of <= rows; 0 for a non-positive shape.  Every one of them refuses a smaller workspace (KURBM_ERR_WORKSPACE).
+ * One addition: kurbm_cd_step / kurbm_cd_epoch (and their _mom twins) keep the negative visibles in the workspace at the leading
+ * dimension of the batch, so a batch with ldv > round_up(n_vis, 4) (a column window of a wider matrix) needs
+ *     up256(rows * ldv * 4) - up256(rows * round_up(n_vis, 4) * 4)      (up256: rounded up to a multiple of 256)
+ * bytes more than this query reports, and is refused without them. */
 size_t kurbm_workspace_bytes(kurbm_ctx* ctx, int rows, int n_vis, int n_hid, int k);
 
 /*
@@ -299,8 +306,8 @@ int kurbm_score_x3(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t m
                    int v_pieces, int rows, int ldv, const kurbm_cd_opts* opts, float* score, float* F, void* workspace,
                    size_t workspace_bytes, kurbm_stream_t stream);
 
-/* kurbm_free_energy on the x3 path (rbm.py:73-76): workspace >= the bf16 pieces of v + one float per row and
- * 128-column tile (kurbm_x3_workspace_bytes of the same rows is enough). */
+/* kurbm_free_energy on the x3 path (rbm.py:73-76): workspace of kurbm_x3_workspace_bytes of the same rows and v_pieces
+ * (it holds the bf16 pieces of v and one float per row and 128-column tile; a smaller one is refused). */
 int kurbm_free_energy_x3(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t mirror_bytes, const float* v,
                          int v_pieces, int rows, int ldv, float* F, void* workspace, size_t workspace_bytes,
                          kurbm_stream_t stream);
@@ -464,7 +471,7 @@ void kurbm_peer_destroy(kurbm_peer* peer);
  * lambda times the batch size); the library does not rescale by the row count -- under data parallelism the apply sees only
  * the sum.  `vel` is caller-owned device memory in the layout of delta_out, packed [n_vis*n_hid | n_hid | n_vis] fp32 with no row
  * padding, 16-byte aligned, zeroed by the caller before the first step.  `which` masks as in kurbm_cd_step: a variable it does not
- * select has neither its parameters nor its velocity read or written.  The padding columns of W stay zero.
+ * select has neither its parameters nor its velocity read or written.  The padding columns of W are left as they are.
  * The velocity travels inside the launch that already reduces the slabs and rewrites the weights (and, on the x3 / bf16 paths,
  * their bf16 pieces, which are made from the NEW weights): one more 16-byte load and store per weight group, no extra launch.
  * Every *_mom entry point takes the arguments of its plain twin plus `mom`, requires opts->apply = 1 and honours

@@ -215,7 +215,10 @@ struct Workspace {
 static size_t align_up(size_t x) { return (x + 255) / 256 * 256; }
 constexpr int SMALL_ROWS_MAX = 512;   // batches up to here carry the transposed planes of the one-launch step in their workspace
 
-static Workspace carve(const kurbm_ctx* ctx, void* base, int rows, int n_vis, int n_hid, int k) {
+// ldv_batch (kurbm_cd_step only): the leading dimension of the caller's batch.  The step keeps v_neg at THAT leading dimension (the
+// statistics GEMM takes v_pos and v_neg as the two segments of one operand, with one lda), so a batch wider than round_up(n_vis, 4)
+// needs rows * (ldv - round_up(n_vis, 4)) more floats here than kurbm_workspace_bytes reports: include/kurbm.h has the formula.
+static Workspace carve(const kurbm_ctx* ctx, void* base, int rows, int n_vis, int n_hid, int k, int ldv_batch = 0) {
     Workspace w;
     w.ldh = round_up(n_hid, 4);
     w.ldv = round_up(n_vis, 4);
@@ -230,7 +233,7 @@ static Workspace carve(const kurbm_ctx* ctx, void* base, int rows, int n_vis, in
     w.h_pos = take((size_t)rows * w.ldh);
     w.h_neg = take((size_t)rows * w.ldh);
     w.h_tmp = take((size_t)rows * w.ldh);   // intermediate h_t (k > 1) / persistent-chain start
-    w.v_neg = take((size_t)rows * w.ldv);
+    w.v_neg = take((size_t)rows * (ldv_batch > w.ldv ? ldv_batch : w.ldv));
     w.part_h = take((size_t)w.max_row_tiles * w.ld_part_h);
     w.part_v = take((size_t)w.max_row_tiles * w.ld_part_v);
     w.slab = take(w.slab_stride * pl.nsplit_bound);
@@ -458,9 +461,10 @@ static int cd_step_f32(kurbm_ctx* ctx, const kurbm_params* p, const float* v_bat
     if (!workspace || !aligned16(workspace)) return fail(KURBM_ERR_ARG, "workspace is null or misaligned");
     if (o->v_chain && !aligned16(o->v_chain)) return fail(KURBM_ERR_ARG, "v_chain is misaligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const Workspace w = carve(ctx, workspace, rows, p->n_vis, p->n_hid, o->k);
+    const Workspace w = carve(ctx, workspace, rows, p->n_vis, p->n_hid, o->k, ldv);
     if (w.bytes > workspace_bytes)
-        return fail(KURBM_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", w.bytes, workspace_bytes);
+        return fail(KURBM_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu%s", w.bytes, workspace_bytes,
+                    ldv > w.ldv ? " (ldv > round_up(n_vis, 4): v_neg is kept at the batch's leading dimension, see kurbm_workspace_bytes)" : "");
 
     const bool gauss = (o->mode == KURBM_MODE_VISIBLE_GAUSSIAN);
     const int act_h = gauss ? ACT_RELU : ACT_SIGMOID;             // rbm.py:59 vs :47
@@ -746,7 +750,10 @@ int kurbm_free_energy(kurbm_ctx* ctx, const kurbm_params* p, const float* v, int
     g.bias = p->b_h;
     g.rowpart = static_cast<float*>(workspace);
     g.ld_rowpart = round_up(rows, 4);
-    const size_t need = (size_t)g.grid_n * g.ld_rowpart * 4;
+    // (the row partials need less, but the contract is one size for every call on these rows: kurbm_workspace_bytes)
+    size_t need = (size_t)g.grid_n * g.ld_rowpart * 4;
+    const size_t query = carve(ctx, nullptr, rows, p->n_vis, p->n_hid, 1).bytes;
+    if (query > need) need = query;
     if (need > workspace_bytes) return fail(KURBM_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
     HIP_TRY(launch_gemm(LAYOUT_VH, cfg, EPI_SOFTPLUS, g, st));
     FinishArgs f;
@@ -869,11 +876,15 @@ struct OuterPlanB { int gm, gn, nkt, kt_total, nsplit, nsplit_bound, kt_per_spli
 // the statistics GEMM on k_gemm_pb: k-tile 64, one workgroup per CU, nseg segments walked fastest, so a slice is a whole
 // number of k positions
 static OuterPlanB plan_outer_bf16(const kurbm_ctx* ctx, int rows, int n_vis, int n_hid, int nseg, int s_max = 1 << 30,
-                                  bool f8pos = false, bool x3 = false) {
+                                  bool f8pos = false, bool x3 = false, int n_vis_whole = 0) {
     OuterPlanB pl;
+    // n_vis_whole: this plan is for a ROW RANGE of a matrix of that many visible rows -- it keeps the whole matrix's tile shape, which
+    // the planes were written for (the byte-plane statistics of 0/1 data exist on the 256 x 64 tile only: a range of <= 128 rows
+    // planned for itself came out as 128 x 128 and the launch was refused, hipErrorInvalidValue)
+    if (n_vis_whole < n_vis) n_vis_whole = n_vis;
     // x3: 256 x 64 tiles -- the three-piece B tile is the heavy operand (3 x 8 KB against 3 x 16), so a k-tile is 56 KB instead
     // of 64 for the same MFMAs, and 784 x 1024 fills 256 workgroups instead of 224 (statistics GEMM 28.5 -> 27.4 us)
-    pl.cfg = (x3 && ctx->knob[KN_X3_STATS_TALL] != 0 && n_vis > 128) ? 2 : 0;
+    pl.cfg = (x3 && ctx->knob[KN_X3_STATS_TALL] != 0 && n_vis_whole > 128) ? 2 : 0;
     pl.gm = ceil_div(n_vis, pl.cfg == 2 ? 256 : 128);
     pl.gn = ceil_div(n_hid, pl.cfg == 2 ? 64 : 128);
     // f8pos: the walk is in units of 128 k -- one fp8 tile of segment 0, two 64-deep tiles of every other segment
@@ -1111,7 +1122,10 @@ static int half_step_any(kurbm_ctx* ctx, int pieces, int in_pieces, const kurbm_
     // the input plane is staged in the larger of the two row-major buffers' shapes: use a private carve
     const int Kp = ld_pad(ctx, round_up(K, 128)), Kb = round_up(rows, 128);   // Kp: leading dimension of the staged input
     const size_t plane = (size_t)Kb * Kp;
-    const size_t need = align_up(in_pieces * plane * 2);
+    // (the staged input needs less, but the contract is one size for every call on these rows: kurbm_{bf16,x3}_workspace_bytes)
+    size_t need = align_up(in_pieces * plane * 2);
+    const size_t query = carve_bf16(ctx, nullptr, rows, p->n_vis, p->n_hid, pieces, pieces == 3 ? in_pieces : 1).bytes;
+    if (query > need) need = query;
     if (need > workspace_bytes) return fail(KURBM_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
     uint16_t* Ab = static_cast<uint16_t*>(workspace);
     HIP_TRY(launch_f32_to_bf16(in, rows, K, ld_in, Ab, Kp, Kb, nullptr, 0, 0, in_pieces, plane, 0, nullptr, 0, st));
@@ -1277,7 +1291,7 @@ static int cd_step_any(kurbm_ctx* ctx, int pieces, int v_pieces, const kurbm_par
     const bool sub = (Mr != p->n_vis);
     // a row range keeps inside the slab memory carved for the whole matrix
     const OuterPlanB pl = sub ? plan_outer_bf16(ctx, rows, Mr, p->n_hid, nseg_st,
-                                                (int)((w.slab_stride * plf.nsplit_bound) / ((size_t)Mr * plf.ld_slab)), f8pos, pieces == 3)
+                                                (int)((w.slab_stride * plf.nsplit_bound) / ((size_t)Mr * plf.ld_slab)), f8pos, pieces == 3, p->n_vis)
                               : plf;
     const size_t slab_stride = sub ? (size_t)Mr * pl.ld_slab : w.slab_stride;
     const bool ap = o->apply != 0;
@@ -1510,7 +1524,9 @@ int kurbm_free_energy_x3(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, si
     memset(&g, 0, sizeof g);
     g.grid_m = ceil_div(rows, 128); g.grid_n = ceil_div(p->n_hid, 128);
     g.ld_rowpart = round_up(rows, 4);
-    const size_t need = a_bytes + (size_t)g.grid_n * g.ld_rowpart * 4;
+    size_t need = a_bytes + (size_t)g.grid_n * g.ld_rowpart * 4;
+    const size_t query = carve_bf16(ctx, nullptr, rows, p->n_vis, p->n_hid, 3, v_pieces).bytes;   // (one size for every call on these rows)
+    if (query > need) need = query;
     if (need > workspace_bytes) return fail(KURBM_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
     uint16_t* Ab = static_cast<uint16_t*>(workspace);
     HIP_TRY(launch_f32_to_bf16(v, rows, p->n_vis, ldv, Ab, Lp, Kb, nullptr, 0, 0, v_pieces, plane, 0, nullptr, 0, st));

@@ -122,10 +122,13 @@ __device__ __forceinline__ void reduce_apply_split_body(ReduceArgs& a, int tiles
                         *reinterpret_cast<f32x4*>(mo.vel_w + (size_t)r * a.n_hid + c) = vel;
                         w = w + vel;
                     } else if (a.slab) w = w + s * a.lr;
+                    // the tail group of a row (n_hid % 4 != 0): W's padding columns go back as they were loaded (include/kurbm.h: output
+                    // padding is left untouched -- it may be NaN), and enter the bf16 pieces below as zeros
+                    f32x4 wst = w;
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
-                        if (c + e >= a.n_hid) w[e] = 0.f;                     // the row padding stays zero
-                    if (a.slab) *reinterpret_cast<f32x4*>(wp) = w;
+                        if (c + e >= a.n_hid) { wst[e] = wv[j][e]; w[e] = 0.f; }
+                    if (a.slab) *reinterpret_cast<f32x4*>(wp) = wst;
                 }
                 if (a.delta_w) {
 #pragma unroll

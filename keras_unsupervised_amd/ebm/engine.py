@@ -105,7 +105,7 @@ class ResidentPlanes:
         self.stride = int(eng.lib.kurbm_x3_planes_bytes(eng.ctx.handle, max_rows, eng.n_vis, self.v_pieces))
         if self.stride == 0:
             raise _lib.KurbmError("kurbm_x3_planes_bytes failed")
-        self.buf = torch.empty(max(len(self.windows), 1) * self.stride, dtype=torch.uint8, device=eng.device)
+        self.buf = eng._alloc_bytes(max(len(self.windows), 1) * self.stride, "planes", zero=False)
         self.slot = {}
         for t, (lo, rows) in enumerate(self.windows):
             if rows <= 0:
@@ -147,6 +147,7 @@ class DeviceRBM:
                              self.b_h.data_ptr(), self.b_v.data_ptr())
         self._ws = None
         self._ws_rows = 0
+        self._ws_ldv = 0
         self.delta = None  # packed [V*H | H | V] sums, allocated on first use
         # bf16 images of W in both orientations, per number of pieces: 1 = rounded (compute 'bf16'),
         # 3 = exact hi/mid/lo split (compute 'x3');  [tensor, stale]
@@ -158,19 +159,40 @@ class DeviceRBM:
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    def workspace(self, rows, k=1):
-        if self._ws is None or rows > self._ws_rows:
+    # Every buffer the library is handed besides the parameters comes from one of these three (`what` names its use).  A subclass
+    # may place them elsewhere (tests/guarded.py carves them out of a guarded arena, each exactly as large as its size query says).
+    def _alloc_bytes(self, n, what, zero=True):
+        """Raw device bytes: workspaces, mirrors, resident planes."""
+        return (torch.zeros if zero else torch.empty)(n, dtype=torch.uint8, device=self.device)
+
+    def _alloc_floats(self, n, what, zero=True):
+        """A dense fp32 device vector: packed delta / velocity, free energies, the score words, a dense dW."""
+        return (torch.zeros if zero else torch.empty)(n, dtype=torch.float32, device=self.device)
+
+    def _alloc_out(self, rows, cols, what):
+        """An output DeviceMatrix [rows, cols]; its ld is what the library is given."""
+        return DeviceMatrix.zeros(rows, cols, self.device)
+
+    def workspace(self, rows, k=1, ldv=0):
+        """Scratch of the fp32 entry points for batches of <= rows.  ldv: the leading dimension of the batch of a kurbm_cd_step /
+        kurbm_cd_epoch when it exceeds round_up(n_vis, 4) -- the step keeps v_neg at that leading dimension and needs that much more
+        (include/kurbm.h, kurbm_workspace_bytes); a DeviceMatrix made here never does."""
+        ldc = round_up(self.n_vis, 4)
+        ldv = max(int(ldv), ldc, self._ws_ldv)
+        if self._ws is None or rows > self._ws_rows or ldv > self._ws_ldv:
+            rows = max(rows, self._ws_rows)
             n = self.lib.kurbm_workspace_bytes(self.ctx.handle, rows, self.n_vis, self.n_hid, k)
             if n == 0:
                 raise _lib.KurbmError("kurbm_workspace_bytes failed")
-            self._ws = torch.zeros(n, dtype=torch.uint8, device=self.device)
-            self._ws_rows = rows
+            n += round_up(rows * ldv * 4, 256) - round_up(rows * ldc * 4, 256)
+            self._ws = self._alloc_bytes(n, "workspace")
+            self._ws_rows, self._ws_ldv = rows, ldv
         return self._ws
 
     def delta_buffer(self):
         if self.delta is None:
             n = self.n_vis * self.n_hid + self.n_hid + self.n_vis
-            self.delta = torch.zeros(n, dtype=torch.float32, device=self.device)
+            self.delta = self._alloc_floats(n, "delta")
         return self.delta
 
     # -- momentum / weight decay (include/kurbm.h: kurbm_momentum) -------------------------------
@@ -178,7 +200,7 @@ class DeviceRBM:
         if self.velocity is None:
             n = self.n_vis * self.n_hid + self.n_hid + self.n_vis
             with torch.cuda.device(self.device):
-                self.velocity = torch.zeros(n, dtype=torch.float32, device=self.device)
+                self.velocity = self._alloc_floats(n, "velocity")
         return self.velocity
 
     def _mom(self, momentum):
@@ -217,7 +239,7 @@ class DeviceRBM:
         fn_refresh = self.lib.kurbm_bf16_mirror_refresh if pieces == 1 else self.lib.kurbm_x3_mirror_refresh
         if m is None:
             n = fn_bytes(self.ctx.handle, self.n_vis, self.n_hid)
-            m = self._mirrors[pieces] = [torch.zeros(n, dtype=torch.uint8, device=self.device), True]
+            m = self._mirrors[pieces] = [self._alloc_bytes(n, "mirror%d" % pieces), True]
         if m[1]:
             check(fn_refresh(self.ctx.handle, C.byref(self.params), m[0].data_ptr(), m[0].numel(), self._stream()))
             m[1] = False
@@ -233,7 +255,7 @@ class DeviceRBM:
                 n = self.lib.kurbm_x3_workspace_bytes(self.ctx.handle, rows, self.n_vis, self.n_hid, k, v_pieces)
             if n == 0:
                 raise _lib.KurbmError("workspace size query failed")
-            have = self._ws_b[key] = (torch.zeros(n, dtype=torch.uint8, device=self.device), rows)
+            have = self._ws_b[key] = (self._alloc_bytes(n, "workspace%d" % pieces), rows)
         return have[0]
 
     def v_pieces(self, v):
@@ -293,10 +315,10 @@ class DeviceRBM:
         out = {}
         with torch.cuda.device(self.device):
             for key, want in (("sample", want_sample), ("prob", want_prob), ("u", want_u)):
-                out[key] = DeviceMatrix.zeros(rows, n_out, self.device) if want else None
+                out[key] = self._alloc_out(rows, n_out, key) if want else None
             rng = Rng(int(seed), int(row0), int(stream_id) & 0xFFFFFFFF, int(step) & 0xFFFFFFFF)
             fn = self.lib.kurbm_half_step_vh_dbg if direction == "vh" else self.lib.kurbm_half_step_hv_dbg
-            ld_out = round_up(n_out, 4)
+            ld_out = next((m.ld for m in out.values() if m is not None), round_up(n_out, 4))
             check(fn(self.ctx.handle, C.byref(self.params), x.ptr(row_start), rows, x.ld, act, noise,
                      C.byref(rng), out["sample"].ptr() if want_sample else None,
                      out["prob"].ptr() if want_prob else None, out["u"].ptr() if want_u else None,
@@ -379,7 +401,7 @@ class DeviceRBM:
                 if apply and (which & 1):
                     self._weights_written(kept=3)
             elif compute == "fp32":
-                ws = self.workspace(rows, k)
+                ws = self.workspace(rows, k, v.ld)
                 if momentum is None:
                     check(self.lib.kurbm_cd_step(self.ctx.handle, C.byref(self.params), v.ptr(row_start), rows, v.ld,
                                                  C.byref(opts), int(which), ws.data_ptr(), ws.numel(), self._stream()))
@@ -514,7 +536,7 @@ class DeviceRBM:
             self._chain_written(v_chain, mode)
             return n
         with torch.cuda.device(self.device):
-            ws = self.workspace(min(batch_size, max(n_rows, 1)), k)
+            ws = self.workspace(min(batch_size, max(n_rows, 1)), k, 0 if compute == "small" else v.ld)
             opts = CdOpts(int(k), int(mode), float(lr), 1, None, v_chain.ptr() if v_chain is not None else None,
                           int(seed), 0, int(step0) & 0xFFFFFFFF, 0)
             fn = self.lib.kurbm_cd_epoch_small if compute == "small" else (self.lib.kurbm_cd_epoch_mom if mom else self.lib.kurbm_cd_epoch)
@@ -553,11 +575,12 @@ class DeviceRBM:
             xp = self.v_pieces(x) if pieces == 3 else 1
             mir, ws = self.mirror(pieces), self.workspace_bf16(rows, 1, pieces, xp if pieces == 3 else 1)
             want = {"sample": bool(noise), "prob": bool(want_prob) or not noise, "u": bool(want_u) and bool(noise)}
-            out = {k: (DeviceMatrix.zeros(rows, n_out, self.device) if want[k] else None) for k in ("sample", "prob", "u")}
+            out = {k: (self._alloc_out(rows, n_out, k) if want[k] else None) for k in ("sample", "prob", "u")}
             rng = Rng(int(seed), int(row0), int(stream_id) & 0xFFFFFFFF, int(step) & 0xFFFFFFFF)
             tail = (act, noise, C.byref(rng), out["sample"].ptr() if out["sample"] is not None else None,
                     out["prob"].ptr() if out["prob"] is not None else None, out["u"].ptr() if out["u"] is not None else None,
-                    round_up(n_out, 4), ws.data_ptr(), ws.numel(), self._stream())
+                    next((m.ld for m in out.values() if m is not None), round_up(n_out, 4)), ws.data_ptr(), ws.numel(),
+                    self._stream())
             d = 0 if direction == "vh" else 1
             if pieces == 3:
                 check(self.lib.kurbm_half_step_x3(self.ctx.handle, C.byref(self.params), mir.data_ptr(), mir.numel(), d,
@@ -593,7 +616,7 @@ class DeviceRBM:
     def free_energy(self, v, rows, row_start=0, compute=None):
         """F(v) per row (rbm.py:73-76).  compute='x3': the v.W product on the bf16 pieces (fp32-equivalent)."""
         with torch.cuda.device(self.device):
-            F = torch.empty(rows, dtype=torch.float32, device=self.device)
+            F = self._alloc_floats(rows, "F", zero=False)
             if compute == "x3":
                 vp = self.v_pieces(v)
                 mir, ws = self.mirror(3), self.workspace_bf16(rows, 1, 3, vp)
@@ -615,7 +638,7 @@ class DeviceRBM:
             opts = CdOpts(1, int(mode), 0.0, 0, None, None, int(seed), 0, int(step) & 0xFFFFFFFF, int(chain))
             if planes is not None:
                 opts.v_planes = planes.ptr(v, row_start, rows, vp)
-            out = torch.empty(4, dtype=torch.float32, device=self.device)
+            out = self._alloc_floats(4, "score", zero=False)
             check(self.lib.kurbm_score_x3(self.ctx.handle, C.byref(self.params), mir.data_ptr(), mir.numel(), v.ptr(row_start), vp,
                                           int(rows), v.ld, C.byref(opts), out.data_ptr(), None, ws.data_ptr(), ws.numel(),
                                           self._stream()))
@@ -627,8 +650,8 @@ class DeviceRBM:
         with torch.cuda.device(self.device):
             ws = self.workspace(rows)
             opts = CdOpts(1, int(mode), 0.0, 0, None, None, int(seed), 0, int(step) & 0xFFFFFFFF, int(chain))
-            out = torch.empty(4, dtype=torch.float32, device=self.device)
-            F = torch.empty((2, rows), dtype=torch.float32, device=self.device) if want_F else None
+            out = self._alloc_floats(4, "score", zero=False)
+            F = self._alloc_floats(2 * rows, "F", zero=False).view(2, rows) if want_F else None
             check(self.lib.kurbm_score_small(self.ctx.handle, C.byref(self.params), v.ptr(row_start), int(rows), v.ld, C.byref(opts),
                                              out.data_ptr(), F.data_ptr() if want_F else None, ws.data_ptr(), ws.numel(),
                                              self._stream()))
@@ -641,14 +664,14 @@ class DeviceRBM:
             vp = self._x3_pieces(v, None, mode)
             ws = self.workspace_bf16(rows, 1, 3, vp)
             units = self.n_vis if which in (_lib.PLANE_V_NEG, _lib.PLANE_V_NEG_T) else self.n_hid
-            out = DeviceMatrix.zeros(rows, units, self.device)
+            out = self._alloc_out(rows, units, "plane")
             check(self.lib.kurbm_x3_dump_plane(self.ctx.handle, int(which), int(rows), self.n_vis, self.n_hid, vp, int(mode),
                                                ws.data_ptr(), ws.numel(), out.ptr(), out.ld, self._stream()))
         return out
 
     def philox_uniform(self, rows, cols, seed, stream_id, step, row0=0):
         with torch.cuda.device(self.device):
-            out = DeviceMatrix.zeros(rows, cols, self.device)
+            out = self._alloc_out(rows, cols, "uniform")
             rng = Rng(int(seed), int(row0), int(stream_id) & 0xFFFFFFFF, int(step) & 0xFFFFFFFF)
             check(self.lib.kurbm_philox_uniform(self.ctx.handle, out.ptr(), rows, cols, out.ld, C.byref(rng),
                                                 self._stream()))
@@ -658,7 +681,7 @@ class DeviceRBM:
         """dW = v_pos^T.h_pos - v_neg^T.h_neg as a dense [n_vis, n_hid] tensor (test / bench hook)."""
         with torch.cuda.device(self.device):
             ws = self.workspace(rows)
-            out = torch.empty((self.n_vis, self.n_hid), dtype=torch.float32, device=self.device)
+            out = self._alloc_floats(self.n_vis * self.n_hid, "delta_w", zero=False).view(self.n_vis, self.n_hid)
             check(self.lib.kurbm_outer_delta(self.ctx.handle, v_pos.ptr(), h_pos.ptr(), v_neg.ptr(), h_neg.ptr(),
                                              rows, self.n_vis, self.n_hid, v_pos.ld, h_pos.ld, out.data_ptr(),
                                              ws.data_ptr(), ws.numel(), self._stream()))
