@@ -515,6 +515,44 @@ int kurbm_x3_apply_delta_mom(kurbm_ctx* ctx, const kurbm_params* p, void* mirror
 int kurbm_bf16_exact(kurbm_ctx* ctx, const float* x, int rows, int cols, int ld, int* flag,
                      kurbm_stream_t stream);
 
+/*
+ * Annealed importance sampling (Salakhutdinov & Murray 2008) of log Z for a Bernoulli-Bernoulli RBM.  An extension: the
+ * reference has no likelihood estimate at all (its score, rbm.py:225-233, is a reconstruction heuristic).
+ * With b_A = base_bias (the visible bias of the base-rate model W = 0) and a(v) = v.W + b_h the intermediate distributions are
+ *     p*_beta(v) = exp((1 - beta) b_A.v + beta b_v.v) prod_j (1 + exp(beta a_j(v))),
+ * so log Z_0 = n_hid ln 2 + sum_i softplus(b_A,i) and p*_1 = exp(-F(v)).  Chain c (global index chain0 + c) runs
+ *     v_0 = [u < sigmoid(b_A)]
+ *     k = 1 .. n_betas - 1:   Delta_k = (beta_k - beta_{k-1}) (b_v - b_A).v_{k-1} + sum_j [softplus(beta_k a_j) - softplus(beta_{k-1} a_j)]
+ *                             h = [u < sigmoid(beta_k a)],   v_k = [u < sigmoid((1 - beta_k) b_A + beta_k (h.W^T + b_v))]
+ *     logw[c] = sum_k Delta_k                       (double; log Z ~ log Z_0 + log mean_c exp(logw[c]) is the caller's)
+ * Draws follow the Philox contract above with row = chain0 + c (any value, not only multiples of 4), col = unit, step = k and
+ * the three sampling sites below (v_0: step 0).  One temperature is two fp32-MFMA GEMM launches -- the half steps with beta in
+ * the epilogue; W is never scaled -- and one small launch that adds Delta_k into logw; the softplus difference is evaluated as
+ * log1p(sigmoid(beta_{k-1} a) expm1((beta_k - beta_{k-1}) a)), which does not cancel at the 1e-4 spacing of a long run.  The
+ * whole run is queued without a host synchronisation, and is bit-reproducible for (seed, betas, chain0): a chain's numbers do
+ * not depend on how many other chains share the call.
+ * betas is a HOST array (read before the call returns): betas[0] = 0, betas[n_betas - 1] = 1, strictly increasing.
+ * v_final (nullable): the chains' last visibles.  KURBM_ERR_ARG for a bad schedule, a leading dimension below the column count
+ * or a null / misaligned buffer, KURBM_ERR_WORKSPACE for ws_bytes < kurbm_ais_workspace_bytes: nothing is written then.
+ */
+#define KURBM_STREAM_AIS_INIT 0x200u
+#define KURBM_STREAM_AIS_H    0x201u
+#define KURBM_STREAM_AIS_V    0x202u
+size_t kurbm_ais_workspace_bytes(kurbm_ctx* ctx, int n_chains, int n_vis, int n_hid);
+int kurbm_ais_run(kurbm_ctx* ctx, const kurbm_params* p, const float* base_bias, const double* betas, int n_betas,
+                  int n_chains, uint64_t chain0, uint64_t seed, double* logw, float* v_final, int ldv,
+                  void* ws, size_t ws_bytes, kurbm_stream_t stream);
+/*
+ * Test hook: temperature k of such a run, teacher-forced -- the same three launches on the caller's v_in [n_chains][ldv].
+ * dlogw[c] = Delta_k; h [n_chains][ldh] and v_out [n_chains][ldvo] the samples (v_out is drawn from the call's own h).
+ * Nullable test planes: prob_h, u_h (ldh) and prob_v, u_v (ldvo), the probabilities and the uniforms they were compared with.
+ * 0 <= beta_prev < beta <= 1, k >= 1.
+ */
+int kurbm_ais_step(kurbm_ctx* ctx, const kurbm_params* p, const float* base_bias, double beta_prev, double beta, int k,
+                   const float* v_in, int ldv, int n_chains, uint64_t chain0, uint64_t seed, float* dlogw,
+                   float* h, int ldh, float* v_out, int ldvo, float* prob_h, float* u_h, float* prob_v, float* u_v,
+                   void* ws, size_t ws_bytes, kurbm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

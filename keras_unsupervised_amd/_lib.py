@@ -115,6 +115,11 @@ SIGNATURES = {
     "kurbm_cd_epoch_x3_mom": (_i, [_vp, _PP, _vp, _sz, _vp, _i, _i, _i, _i, _OP, _vp, _sz, _vp, _MP]),
     "kurbm_apply_delta_mom": (_i, [_vp, _PP, _vp, C.c_float, _i, _vp, _MP]),
     "kurbm_x3_apply_delta_mom": (_i, [_vp, _PP, _vp, _sz, _vp, C.c_float, _i, _vp, _MP]),
+    # annealed importance sampling: betas is a HOST array of doubles
+    "kurbm_ais_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "kurbm_ais_run": (_i, [_vp, _PP, _vp, C.POINTER(C.c_double), _i, _i, C.c_uint64, C.c_uint64, _vp, _vp, _i, _vp, _sz, _vp]),
+    "kurbm_ais_step": (_i, [_vp, _PP, _vp, C.c_double, C.c_double, _i, _vp, _i, _i, C.c_uint64, C.c_uint64, _vp, _vp, _i, _vp, _i,
+                            _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 ABI_VERSION = 5

@@ -301,6 +301,78 @@ static int outer_slabs(kurbm_ctx* ctx, const float* v_pos, const float* h_pos, c
     return KURBM_OK;
 }
 
+// ---- annealed importance sampling (include/kurbm.h: kurbm_ais_run) ---------------------
+// Workspace of a run on `rows` chains: the chain state v, the hidden plane h, and the row partials of both GEMM launches
+// (one row of partials per group of 16 columns).  kurbm_ais_step uses the partials only.
+struct AisWorkspace {
+    float *v, *h, *sppart, *vpart;
+    int ldv, ldh, ld_part, ng_h, ng_v;
+    size_t bytes;
+};
+static AisWorkspace carve_ais(void* base, int rows, int n_vis, int n_hid) {
+    AisWorkspace w;
+    w.ldv = round_up(n_vis, 4);
+    w.ldh = round_up(n_hid, 4);
+    w.ld_part = round_up(rows, 4);
+    w.ng_h = ceil_div(n_hid, 16);
+    w.ng_v = ceil_div(n_vis, 16);
+    size_t off = 0;
+    char* b = static_cast<char*>(base);
+    auto take = [&](size_t nfloat) { float* p = reinterpret_cast<float*>(b + off); off = align_up(off + nfloat * 4); return p; };
+    w.v = take((size_t)rows * w.ldv);
+    w.h = take((size_t)rows * w.ldh);
+    w.sppart = take((size_t)w.ng_h * w.ld_part);
+    w.vpart = take((size_t)w.ng_v * w.ld_part);
+    w.bytes = off;
+    return w;
+}
+
+// One temperature: v -> h launch (h and the softplus-difference partials), the accumulate step (it reads the (b_v - b_A).v
+// partials the PREVIOUS temperature -- or the start -- left in vpart, so it runs before they are rewritten), h -> v launch
+// (v and its partials).  ng_v_in: groups of vpart that hold the partials of v_in.
+static int ais_temperature(kurbm_ctx* ctx, const kurbm_params* p, const float* base_bias, double beta_prev, double beta, int k,
+                           const float* v_in, int ldv, int rows, uint64_t chain0, uint64_t seed, const AisWorkspace& w, int ng_v_in,
+                           double* logw, float* dlogw, float* h, int ldh, float* v_out, int ldvo, float* prob_h, float* u_h,
+                           float* prob_v, float* u_v, hipStream_t st) {
+    AisGemmArgs g;
+    memset(static_cast<void*>(&g), 0, sizeof g);
+    g.B0 = p->W; g.ldb = p->ldw;
+    g.M = rows;
+    g.nseg = 1; g.nsplit = 1;
+    g.act = ACT_SIGMOID; g.noise = NOISE_BERNOULLI;
+    g.base_bias = base_bias;
+    g.beta_prev = (float)beta_prev; g.beta = (float)beta; g.dbeta = (float)(beta - beta_prev);
+    g.one_minus_beta = (float)(1.0 - beta);
+    g.ld_rowpart = w.ld_part;
+    for (int layout = LAYOUT_VH; layout <= LAYOUT_HV; ++layout) {
+        const bool vh = layout == LAYOUT_VH;
+        g.A0 = vh ? v_in : h; g.lda = vh ? ldv : ldh;
+        g.K = vh ? p->n_vis : p->n_hid; g.N = vh ? p->n_hid : p->n_vis;
+        g.nkt = g.K / 32; g.kt_total = g.nkt; g.kt_per_split = g.nkt;
+        const int cfg = pick_cfg(ctx->ncu, rows, g.N, &g.grid_m, &g.grid_n, ctx->force_cfg[layout]);
+        g.m_fastest = (g.grid_m < g.grid_n) ? 1 : 0;
+        g.bias = vh ? p->b_h : p->b_v;
+        g.out_sample = vh ? h : v_out; g.out_prob = vh ? prob_h : prob_v; g.out_u = vh ? u_h : u_v; g.ldo = vh ? ldh : ldvo;
+        g.rowpart = vh ? w.sppart : w.vpart;
+        g.rng = make_rng(seed, chain0, vh ? KURBM_STREAM_AIS_H : KURBM_STREAM_AIS_V, (uint32_t)k);
+        HIP_TRY(launch_gemm_ais(layout, cfg, g, st));
+        if (vh) HIP_TRY(launch_ais_accumulate(w.sppart, w.ng_h, w.vpart, ng_v_in, w.ld_part, g.dbeta, logw, dlogw, rows, st));
+    }
+    return KURBM_OK;
+}
+
+static int check_ais_common(kurbm_ctx* ctx, const kurbm_params* p, const float* base_bias, int n_chains, const void* ws,
+                            size_t ws_bytes) {
+    if (!ctx) return fail(KURBM_ERR_ARG, "ctx is null");
+    if (int e = check_params(p)) return e;
+    if (!base_bias) return fail(KURBM_ERR_ARG, "base_bias is null");
+    if (n_chains <= 0) return fail(KURBM_ERR_ARG, "n_chains must be positive");
+    if (!ws || !aligned16(ws)) return fail(KURBM_ERR_ARG, "workspace is null or misaligned");
+    const size_t need = carve_ais(nullptr, n_chains, p->n_vis, p->n_hid).bytes;
+    if (need > ws_bytes) return fail(KURBM_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
+    return KURBM_OK;
+}
+
 // ---- C ABI -----------------------------------------------------------------------------
 extern "C" {
 
@@ -761,6 +833,57 @@ int kurbm_free_energy(kurbm_ctx* ctx, const kurbm_params* p, const float* v, int
     f.rows = rows; f.n_vis = p->n_vis; f.ldv = ldv; f.ncol_tiles = g.grid_n; f.ld_rowpart = g.ld_rowpart;
     HIP_TRY(launch_free_energy_finish(f, st));
     return KURBM_OK;
+}
+
+size_t kurbm_ais_workspace_bytes(kurbm_ctx* ctx, int n_chains, int n_vis, int n_hid) {
+    if (!ctx || n_chains <= 0 || n_vis <= 0 || n_hid <= 0) return 0;
+    return carve_ais(nullptr, n_chains, n_vis, n_hid).bytes;
+}
+
+int kurbm_ais_run(kurbm_ctx* ctx, const kurbm_params* p, const float* base_bias, const double* betas, int n_betas, int n_chains,
+                  uint64_t chain0, uint64_t seed, double* logw, float* v_final, int ldv, void* ws, size_t ws_bytes,
+                  kurbm_stream_t stream) {
+    if (int e = check_ais_common(ctx, p, base_bias, n_chains, ws, ws_bytes)) return e;
+    if (!betas || n_betas < 2) return fail(KURBM_ERR_ARG, "betas: null, or fewer than two temperatures");
+    if (betas[0] != 0.0 || betas[n_betas - 1] != 1.0) return fail(KURBM_ERR_ARG, "betas must run from 0 to 1");
+    for (int k = 1; k < n_betas; ++k)
+        if (!(betas[k] > betas[k - 1])) return fail(KURBM_ERR_ARG, "betas must be strictly increasing (betas[%d])", k);
+    if (!logw || (reinterpret_cast<uintptr_t>(logw) & 7u)) return fail(KURBM_ERR_ARG, "logw is null or misaligned");
+    if (v_final && bad_matrix(v_final, ldv, p->n_vis)) return fail(KURBM_ERR_ARG, "v_final: misaligned, ld %% 4 != 0 or ld < n_vis");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const AisWorkspace w = carve_ais(ws, n_chains, p->n_vis, p->n_hid);
+    HIP_TRY(launch_ais_start(w.v, w.ldv, p->b_v, base_bias, w.vpart, logw, n_chains, p->n_vis, 1,
+                             make_rng(seed, chain0, KURBM_STREAM_AIS_INIT, 0), st));
+    for (int k = 1; k < n_betas; ++k) {
+        // (the last temperature's visibles go straight to v_final; nothing reads them again)
+        const bool last = k == n_betas - 1 && v_final;
+        if (int e = ais_temperature(ctx, p, base_bias, betas[k - 1], betas[k], k, w.v, w.ldv, n_chains, chain0, seed, w,
+                                    k == 1 ? 1 : w.ng_v, logw, nullptr, w.h, w.ldh, last ? v_final : w.v, last ? ldv : w.ldv,
+                                    nullptr, nullptr, nullptr, nullptr, st))
+            return e;
+    }
+    return KURBM_OK;
+}
+
+int kurbm_ais_step(kurbm_ctx* ctx, const kurbm_params* p, const float* base_bias, double beta_prev, double beta, int k,
+                   const float* v_in, int ldv, int n_chains, uint64_t chain0, uint64_t seed, float* dlogw, float* h, int ldh,
+                   float* v_out, int ldvo, float* prob_h, float* u_h, float* prob_v, float* u_v, void* ws, size_t ws_bytes,
+                   kurbm_stream_t stream) {
+    if (int e = check_ais_common(ctx, p, base_bias, n_chains, ws, ws_bytes)) return e;
+    if (!(beta_prev >= 0.0 && beta > beta_prev && beta <= 1.0)) return fail(KURBM_ERR_ARG, "need 0 <= beta_prev < beta <= 1");
+    if (k < 1) return fail(KURBM_ERR_ARG, "k must be >= 1");
+    if (!dlogw) return fail(KURBM_ERR_ARG, "dlogw is null");
+    if (bad_matrix(v_in, ldv, p->n_vis)) return fail(KURBM_ERR_ARG, "v_in: null, misaligned, ld %% 4 != 0 or ld < n_vis");
+    if (bad_matrix(h, ldh, p->n_hid)) return fail(KURBM_ERR_ARG, "h: null, misaligned, ld %% 4 != 0 or ld < n_hid");
+    if (bad_matrix(v_out, ldvo, p->n_vis)) return fail(KURBM_ERR_ARG, "v_out: null, misaligned, ld %% 4 != 0 or ld < n_vis");
+    if ((prob_h && !aligned16(prob_h)) || (u_h && !aligned16(u_h)) || (prob_v && !aligned16(prob_v)) || (u_v && !aligned16(u_v)))
+        return fail(KURBM_ERR_ARG, "a test plane is misaligned");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const AisWorkspace w = carve_ais(ws, n_chains, p->n_vis, p->n_hid);
+    HIP_TRY(launch_ais_start(const_cast<float*>(v_in), ldv, p->b_v, base_bias, w.vpart, nullptr, n_chains, p->n_vis, 0,
+                             make_rng(seed, chain0, KURBM_STREAM_AIS_INIT, 0), st));
+    return ais_temperature(ctx, p, base_bias, beta_prev, beta, k, v_in, ldv, n_chains, chain0, seed, w, 1, nullptr, dlogw, h, ldh,
+                           v_out, ldvo, prob_h, u_h, prob_v, u_v, st);
 }
 
 int kurbm_outer_delta(kurbm_ctx* ctx, const float* v_pos, const float* h_pos, const float* v_neg, const float* h_neg,

@@ -99,6 +99,25 @@ __device__ __forceinline__ float softplusf(float x) {
     return fmaxf(x, 0.0f) + (t < 0.0078125f ? series : hw);
 }
 
+// softplus(y + d) - softplus(y) = log1p(sigmoid(y) expm1(d)) for y and d of one sign (an AIS temperature: y = beta_prev a,
+// d = dbeta a).  The literal difference of two fp32 softplus values cancels: at d ~ 1e-4 a it keeps 2-4e-4 of the term.  Here no
+// step cancels, and every step is a short polynomial or a hardware transcendental (libm's log1pf + expm1f were 8 of the 28 us
+// of the v -> h launch of a 512-chain temperature):
+//   expm1(d)  its series below 1/4 (relative error < d^8 / 9! = 4e-11), else e^d - 1, at least 0.22 in magnitude
+//   log1p(q)  q = sigmoid(y) expm1(d) > -1/2.  Its series below 1/16 (relative error < q^8 / 9 = 3e-11); else with s = fl(1 + q),
+//             log(s) + (q - (s - 1)) / s: the second term restores what rounding 1 + q dropped, and v_log_f32's absolute error
+//             (~1e-7) meets a result of at least 0.06
+__device__ __forceinline__ float softplus_step(float y, float d) {
+    const float e_ser = d * (1.0f + d * (0.5f + d * (0.16666667f + d * (0.041666668f + d * (0.0083333338f + d * (0.0013888889f +
+                        d * (1.9841270e-4f + d * 2.4801587e-5f)))))));
+    const float em1 = fabsf(d) < 0.25f ? e_ser : __expf(d) - 1.0f;
+    const float q = sigmoidf_fast(y) * em1;
+    const float l_ser = q * (1.0f - q * (0.5f - q * (0.33333334f - q * (0.25f - q * (0.2f - q * (0.16666667f - q * (0.14285715f -
+                        q * 0.125f)))))));
+    const float s = 1.0f + q;
+    const float l_hw = 0.69314718f * __builtin_amdgcn_logf(s) + (q - (s - 1.0f)) * __builtin_amdgcn_rcpf(s);
+    return fabsf(q) < 0.0625f ? l_ser : l_hw;
+}
 
 // float -> bf16 bits, round to nearest even (inputs are finite on this path)
 __device__ __forceinline__ uint32_t f32_to_bf16_bits(float x) {

@@ -7,7 +7,7 @@ namespace kurbm {
 
 enum { ACT_SIGMOID = 0, ACT_RELU = 1, ACT_LINEAR = 2 };
 enum { NOISE_NONE = 0, NOISE_BERNOULLI = 1, NOISE_GAUSSIAN = 2 };
-enum { EPI_HALFSTEP = 0, EPI_SLAB = 1, EPI_SOFTPLUS = 2 };
+enum { EPI_HALFSTEP = 0, EPI_SLAB = 1, EPI_SOFTPLUS = 2, EPI_AIS = 3 };
 // operand layouts: VH  A=[m][k] B=[k][n];  HV  A=[m][k] B=[n][k];  OUTER  A=[k][m] B=[k][n]
 enum { LAYOUT_VH = 0, LAYOUT_HV = 1, LAYOUT_OUTER = 2 };
 // tile configurations (BM x BN, waves as WAVES_M x WAVES_N); see tile_shape()
@@ -59,6 +59,32 @@ struct GemmArgs {
     unsigned long long* stamps;
     int dbg_off;        // ablation mask: 1 fetches, 2 parks, 4 fragment reads, 8 barrier (results are garbage)
 };
+
+// One temperature of annealed importance sampling (kurbm_ais_run; EPI_AIS of k_gemm): the half-step GEMM with the
+// pre-activations scaled by beta in the epilogue -- W itself is never scaled.  Of the block above it uses the operands, bias,
+// out_sample / out_prob / out_u / ldo, rng (rng.row0 = the first chain's index, ANY value: a lane's four rows may straddle two
+// Philox blocks) and rowpart / ld_rowpart.  The launch also leaves the chain's contribution to log w as row partials PER GROUP
+// OF 16 COLUMNS, rowpart[column / 16][row] -- a granularity no tile shape changes, so a chain's sum does not depend on how many
+// chains share the launch:
+//   v -> h (LAYOUT_VH), a = v.W + b_h:    h = [u < sigmoid(beta a)],   partial = sum of softplus(beta a) - softplus(beta_prev a),
+//        each term as log1p(sigmoid(beta_prev a) expm1(dbeta a)): no cancellation at dbeta = 1e-4
+//   h -> v (LAYOUT_HV), x = h.W^T:        v = [u < sigmoid((1 - beta) b_A + beta (x + b_v))],   partial = sum of (b_v - b_A) v
+struct AisGemmArgs : GemmArgs {
+    const float* base_bias;        // b_A [n_vis] (h -> v only)
+    float beta_prev, beta, dbeta;  // dbeta = beta - beta_prev formed in double by the host, then narrowed
+    float one_minus_beta;
+};
+hipError_t launch_gemm_ais(int layout, int cfg, const AisGemmArgs& g, hipStream_t st);
+
+// kurbm_ais.hip: the small launches of an AIS run
+//   launch_ais_start: draw = 1: v[row][c] = [u < sigmoid(b_A[c])] (v_0); draw = 0: v is read.  Either way vpart[row] = (b_v - b_A).v[row]
+//                     (ONE group of partials), and logw[row] = 0 where logw is given.
+//   launch_ais_accumulate: delta = dbeta * (sum of the ng_v groups of vpart) + (sum of the ng_sp groups of sppart), groups in index
+//                     order; logw[row] += delta (double; nullable), dlogw[row] = delta (nullable).
+hipError_t launch_ais_start(float* v, int ldv, const float* b_v, const float* base_bias, float* vpart, double* logw, int rows,
+                            int n_vis, int draw, const RngArgs& rng, hipStream_t st);
+hipError_t launch_ais_accumulate(const float* sppart, int ng_sp, const float* vpart, int ng_v, int ld_part, float dbeta,
+                                 double* logw, float* dlogw, int rows, hipStream_t st);
 
 // Diagnostic hook: the next GEMM launches write their s_memtime stamps here (null = off).
 void set_stamp_buffer(unsigned long long* p);

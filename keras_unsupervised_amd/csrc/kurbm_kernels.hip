@@ -8,6 +8,8 @@
 //                                                                        as stored, never transposed)
 //   statistics       dW = v+^T.h+ - v-^T.h-   A = v [k][m], B = h [k][n], K = batch, two signed
 //                                       segments, split over the batch into fp32 slabs
+//   AIS temperature  the two half steps with the pre-activations scaled by beta in the epilogue, plus row partials of the
+//                    temperature's contribution to log w (EPI_AIS; kurbm_kernels.h: AisGemmArgs; no reference counterpart)
 //
 // Reference op sequences replaced (reference ku/ebm/rbm.py): :46-47 / :82-83 (v->h),
 // :52-53 / :121-123 (h->v), :124 (h_neg), :125-134 (updates), :73-75 (free energy).
@@ -194,9 +196,10 @@ __device__ __forceinline__ void fetch_frags(const float* __restrict__ s, int xw,
 // ------------------------------------------------------------------------------------
 // the GEMM kernel
 // ------------------------------------------------------------------------------------
-template <int BM, int BN, int WAVES_M, int WAVES_N, bool A_KM, bool B_KM, int EPI, int NOISE>
-__global__ __launch_bounds__(NTHREADS) void k_gemm(GemmArgs g) {
-    warm_kernel_arguments<sizeof(GemmArgs)>();   // (kurbm_device.h: one wait for the argument segment, not one per use)
+// (ARGS: GemmArgs, or the block derived from it that EPI_AIS reads)
+template <int BM, int BN, int WAVES_M, int WAVES_N, bool A_KM, bool B_KM, int EPI, int NOISE, typename ARGS = GemmArgs>
+__global__ __launch_bounds__(NTHREADS) void k_gemm(ARGS g) {
+    warm_kernel_arguments<sizeof(ARGS)>();   // (kurbm_device.h: one wait for the argument segment, not one per use)
     static_assert(WAVES_M * WAVES_N == 4, "4 waves");
     constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;
     constexpr int TM = WM / 16, TN = WN / 16;
@@ -205,7 +208,7 @@ __global__ __launch_bounds__(NTHREADS) void k_gemm(GemmArgs g) {
     using StB = Stage<BN, B_KM>;
     constexpr int A_FL = StA::TILE_FLOATS, B_FL = StB::TILE_FLOATS;
     // epilogue scratch: per-wave transpose patch / column-sum staging (half step), row-sum staging (softplus)
-    constexpr int EPI_FL = (EPI == EPI_HALFSTEP)
+    constexpr int EPI_FL = (EPI == EPI_HALFSTEP || EPI == EPI_AIS)
                                ? ((4 * WM * (WN + 4) > WAVES_M * (64 / (WN / 4)) * BN) ? 4 * WM * (WN + 4) : WAVES_M * (64 / (WN / 4)) * BN)
                                : ((EPI == EPI_SOFTPLUS) ? WAVES_N * BM : 0);
     constexpr int SMEM_FL = (2 * (A_FL + B_FL) > EPI_FL) ? 2 * (A_FL + B_FL) : EPI_FL;
@@ -437,13 +440,13 @@ __global__ __launch_bounds__(NTHREADS) void k_gemm(GemmArgs g) {
     // 16x16 accumulator).  Every output plane is then transposed through the wave's private LDS
     // patch so global memory sees whole rows: 16 B per lane, 4*WN contiguous bytes per row, instead
     // of 64-B fragments -- and the reference plane of the column-difference sums is read the same way.
-    if (EPI == EPI_HALFSTEP) {
+    if (EPI == EPI_HALFSTEP || EPI == EPI_AIS) {
         constexpr int LDE = WN + 4;                 // patch row (floats): +4 keeps b32 writes conflict-free
         constexpr int LPR = WN / 4;                 // lanes per output row (16 B each)
         constexpr int RPI = 64 / LPR;               // rows per wave-instruction
         constexpr int NPASS = (WM + RPI - 1) / RPI;
         float* patch = smem + wave * (WM * LDE);
-        const bool want_diff = (g.ref != nullptr);
+        const bool want_diff = (EPI == EPI_HALFSTEP) && (g.ref != nullptr);
 
         float pv[TM][TN][4], sv[TM][TN][4], uv[TM][TN][4];
         // the activation is a launch-wide constant: branch on it ONCE, around the whole element nest
@@ -485,7 +488,48 @@ __global__ __launch_bounds__(NTHREADS) void k_gemm(GemmArgs g) {
                 }
             }
         };
-        if (g.act == ACT_SIGMOID) elementwise(std::integral_constant<int, ACT_SIGMOID>{});
+        if constexpr (EPI == EPI_AIS) {
+            // One AIS temperature (kurbm_kernels.h: AisGemmArgs).  The draw as above, except that the first chain's index need
+            // not be a multiple of 4: the four rows of an accumulator then take their words from two consecutive Philox blocks.
+            // The 16 columns a DPP row of lanes holds are one group of the row partials: summed here, stored as 16 bytes
+            // (four rows) by the row's first lane -- no LDS, no atomics, one fixed order.
+            constexpr bool HV = !B_KM;
+            const int woff = (int)(g.rng.row0 & 3);
+#pragma unroll
+            for (int ni = 0; ni < TN; ++ni) {
+                const int cg = n0 + wn * WN + ni * 16, col = cg + l15;
+                const bool cok = col < g.N;
+                const float bias = cok ? g.bias[col] : 0.f;
+                const float ba = (HV && cok) ? g.base_bias[col] : 0.f;
+#pragma unroll
+                for (int mi = 0; mi < TM; ++mi) {
+                    const int rowb = m0 + wm * WM + mi * 16 + slot * 4;
+                    const uint64_t grow = g.rng.row0 + (uint64_t)rowb;
+                    uint32_t w[4], w2[4] = {0u, 0u, 0u, 0u};
+                    philox4x32_10((uint32_t)col, (uint32_t)(grow >> 2), g.rng.stream_id, g.rng.step, g.rng.seed_lo, g.rng.seed_hi, w);
+                    if (woff)
+                        philox4x32_10((uint32_t)col, (uint32_t)((grow >> 2) + 1), g.rng.stream_id, g.rng.step, g.rng.seed_lo,
+                                      g.rng.seed_hi, w2);
+                    const uint32_t ww[7] = {w[0], w[1], w[2], w[3], w2[0], w2[1], w2[2]};
+                    f32x4 part;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float a = acc[mi][ni][r] + bias;
+                        const float p = sigmoidf_fast(HV ? g.one_minus_beta * ba + g.beta * a : g.beta * a);
+                        const uint32_t wr = woff == 0 ? ww[r] : (woff == 1 ? ww[r + 1] : (woff == 2 ? ww[r + 2] : ww[r + 3]));
+                        const float ua = u32_to_unit(wr);
+                        const bool on = ua < p;
+                        pv[mi][ni][r] = p; sv[mi][ni][r] = on ? 1.0f : 0.0f; uv[mi][ni][r] = ua;
+                        float t;
+                        if (HV) t = on ? bias - ba : 0.f;
+                        else t = softplus_step(g.beta_prev * a, g.dbeta * a);   // (kurbm_device.h: no cancellation, no libm)
+                        part[r] = row16_sum(cok ? t : 0.f);
+                    }
+                    if (l15 == 0 && cg < g.N && rowb < g.M)   // (ld_rowpart = the rows rounded up to 4: the store stays inside its row of partials)
+                        *reinterpret_cast<f32x4*>(g.rowpart + (size_t)(cg >> 4) * g.ld_rowpart + rowb) = part;
+                }
+            }
+        } else if (g.act == ACT_SIGMOID) elementwise(std::integral_constant<int, ACT_SIGMOID>{});
         else if (g.act == ACT_RELU) elementwise(std::integral_constant<int, ACT_RELU>{});
         else elementwise(std::integral_constant<int, ACT_LINEAR>{});
 
@@ -727,10 +771,10 @@ hipError_t launch_score(const ScoreArgs& a, hipStream_t st) {
 // ------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------
-template <int BM, int BN, int WM_, int WN_, bool A_KM, bool B_KM, int EPI, int NOISE>
-static hipError_t launch_cfg(const GemmArgs& g, hipStream_t st) {
+template <int BM, int BN, int WM_, int WN_, bool A_KM, bool B_KM, int EPI, int NOISE, typename ARGS = GemmArgs>
+static hipError_t launch_cfg(const ARGS& g, hipStream_t st) {
     const int nblk = g.grid_m * g.grid_n * g.nsplit;
-    hipLaunchKernelGGL((k_gemm<BM, BN, WM_, WN_, A_KM, B_KM, EPI, NOISE>), dim3(nblk), dim3(NTHREADS), 0, st, g);
+    hipLaunchKernelGGL((k_gemm<BM, BN, WM_, WN_, A_KM, B_KM, EPI, NOISE, ARGS>), dim3(nblk), dim3(NTHREADS), 0, st, g);
     return hipGetLastError();
 }
 
@@ -771,6 +815,31 @@ hipError_t launch_gemm(int layout, int cfg, int epi, const GemmArgs& g_in, hipSt
     KURBM_CASE(LAYOUT_HV, false, false, EPI_HALFSTEP, NOISE_GAUSSIAN)
     KURBM_CASE(LAYOUT_VH, false, true, EPI_SOFTPLUS, NOISE_NONE)
     KURBM_CASE(LAYOUT_OUTER, true, true, EPI_SLAB, NOISE_NONE)
+#undef KURBM_CASE
+    return hipErrorInvalidValue;
+}
+
+// one AIS temperature's v -> h or h -> v launch: the tile shapes of the half steps, EPI_AIS, Bernoulli draws
+hipError_t launch_gemm_ais(int layout, int cfg, const AisGemmArgs& g_in, hipStream_t st) {
+    AisGemmArgs g = g_in;
+    g.stamps = g_stamp_buffer;
+    g.dbg_off = g_dbg_off;
+#define KURBM_CASE(L, AK, BKM)                                                                                                \
+    if (layout == L) {                                                                                                       \
+        switch (cfg) {                                                                                                       \
+            case CFG_128x128: return launch_cfg<128, 128, 2, 2, AK, BKM, EPI_AIS, NOISE_BERNOULLI, AisGemmArgs>(g, st);      \
+            case CFG_128x112: return launch_cfg<128, 112, 4, 1, AK, BKM, EPI_AIS, NOISE_BERNOULLI, AisGemmArgs>(g, st);      \
+            case CFG_112x128: return launch_cfg<112, 128, 1, 4, AK, BKM, EPI_AIS, NOISE_BERNOULLI, AisGemmArgs>(g, st);      \
+            case CFG_128x64: return launch_cfg<128, 64, 2, 2, AK, BKM, EPI_AIS, NOISE_BERNOULLI, AisGemmArgs>(g, st);        \
+            case CFG_64x128: return launch_cfg<64, 128, 2, 2, AK, BKM, EPI_AIS, NOISE_BERNOULLI, AisGemmArgs>(g, st);        \
+            case CFG_64x64: return launch_cfg<64, 64, 2, 2, AK, BKM, EPI_AIS, NOISE_BERNOULLI, AisGemmArgs>(g, st);          \
+            case CFG_64x112: return launch_cfg<64, 112, 4, 1, AK, BKM, EPI_AIS, NOISE_BERNOULLI, AisGemmArgs>(g, st);        \
+            case CFG_112x64: return launch_cfg<112, 64, 1, 4, AK, BKM, EPI_AIS, NOISE_BERNOULLI, AisGemmArgs>(g, st);        \
+            default: return hipErrorInvalidValue;                                                                            \
+        }                                                                                                                    \
+    }
+    KURBM_CASE(LAYOUT_VH, false, true)
+    KURBM_CASE(LAYOUT_HV, false, false)
 #undef KURBM_CASE
     return hipErrorInvalidValue;
 }

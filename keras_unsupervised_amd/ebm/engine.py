@@ -21,6 +21,10 @@ MODE_COMPLEX = 2
 CHAIN_STRIDE = 64
 STREAM_TRANSFORM = 0x100
 STREAM_INV_TRANSFORM = 0x101
+# the three sites of an AIS run (kurbm_ais_run): v_0 (step 0), then h and v of temperature k (step k); row = the chain's index
+STREAM_AIS_INIT = 0x200
+STREAM_AIS_H = 0x201
+STREAM_AIS_V = 0x202
 CHAIN_W, CHAIN_BH, CHAIN_BV, CHAIN_SCORE = 0, 1, 2, 3
 
 
@@ -628,6 +632,63 @@ class DeviceRBM:
             check(self.lib.kurbm_free_energy(self.ctx.handle, C.byref(self.params), v.ptr(row_start), rows, v.ld,
                                              F.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
         return F
+
+    # -- annealed importance sampling (include/kurbm.h: kurbm_ais_run) --------------------------
+    def ais_workspace(self, n_chains):
+        n = int(self.lib.kurbm_ais_workspace_bytes(self.ctx.handle, int(n_chains), self.n_vis, self.n_hid))
+        if n == 0:
+            raise _lib.KurbmError("kurbm_ais_workspace_bytes failed")
+        return self._alloc_bytes(n, "ais_workspace", zero=False)
+
+    def _base_bias(self, base_bias):
+        """b_A [n_vis] on the device: a device tensor as is, a host array uploaded, None = zeros (the uniform base model)."""
+        if isinstance(base_bias, torch.Tensor) and base_bias.device == self.device:
+            if base_bias.dtype != torch.float32 or base_bias.numel() != self.n_vis:
+                raise ValueError("base_bias must hold %d fp32 values" % self.n_vis)
+            return base_bias
+        b = np.zeros(self.n_vis, np.float32) if base_bias is None else np.ascontiguousarray(base_bias, dtype=np.float32).reshape(-1)
+        if b.size != self.n_vis:
+            raise ValueError("base_bias has %d values, the RBM has %d visible units" % (b.size, self.n_vis))
+        t = self._alloc_floats(self.n_vis, "base_bias", zero=False)
+        t.copy_(torch.from_numpy(b))
+        return t
+
+    def ais_run(self, betas, n_chains, base_bias=None, chain0=0, seed=0, want_v=False, ws=None):
+        """log w of n_chains AIS chains (global indices chain0 ...) over the schedule `betas` (host float64, 0 .. 1, strictly
+        increasing) in ONE library call: two GEMM launches and one small launch per temperature, nothing read back here.
+        Returns (logw: float64 device tensor [n_chains], v_final: DeviceMatrix or None)."""
+        betas = np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
+        n_chains = int(n_chains)
+        with torch.cuda.device(self.device):
+            ba = self._base_bias(base_bias)
+            ws = self.ais_workspace(n_chains) if ws is None else ws
+            logw = self._alloc_floats(2 * n_chains, "logw", zero=False).view(torch.float64)
+            vf = self._alloc_out(n_chains, self.n_vis, "v_final") if want_v else None
+            check(self.lib.kurbm_ais_run(self.ctx.handle, C.byref(self.params), ba.data_ptr(),
+                                         betas.ctypes.data_as(C.POINTER(C.c_double)), int(betas.size), n_chains, int(chain0),
+                                         int(seed), logw.data_ptr(), vf.ptr() if want_v else None, vf.ld if want_v else 0,
+                                         ws.data_ptr(), ws.numel(), self._stream()))
+        return logw, vf
+
+    def ais_step(self, v, beta_prev, beta, k, base_bias=None, chain0=0, seed=0, want_planes=True, ws=None):
+        """Test hook: temperature k of such a run on the chains in DeviceMatrix v (kurbm_ais_step, teacher-forced).  Returns a
+        dict: dlogw (fp32 device tensor), h, v (DeviceMatrix) and, with want_planes, prob_h, u_h, prob_v, u_v."""
+        if v.cols != self.n_vis:
+            raise ValueError("input has %d columns, expected %d" % (v.cols, self.n_vis))
+        rows = v.rows
+        with torch.cuda.device(self.device):
+            ba = self._base_bias(base_bias)
+            ws = self.ais_workspace(rows) if ws is None else ws
+            out = {"dlogw": self._alloc_floats(rows, "dlogw", zero=False)}
+            for key, cols, want in (("h", self.n_hid, True), ("prob_h", self.n_hid, want_planes), ("u_h", self.n_hid, want_planes),
+                                    ("v", self.n_vis, True), ("prob_v", self.n_vis, want_planes), ("u_v", self.n_vis, want_planes)):
+                out[key] = self._alloc_out(rows, cols, key) if want else None
+            ptr = lambda key: out[key].ptr() if out[key] is not None else None
+            check(self.lib.kurbm_ais_step(self.ctx.handle, C.byref(self.params), ba.data_ptr(), float(beta_prev), float(beta), int(k),
+                                          v.ptr(), v.ld, rows, int(chain0), int(seed), out["dlogw"].data_ptr(),
+                                          ptr("h"), out["h"].ld, ptr("v"), out["v"].ld, ptr("prob_h"), ptr("u_h"), ptr("prob_v"),
+                                          ptr("u_v"), ws.data_ptr(), ws.numel(), self._stream()))
+        return out
 
     def score_x3(self, v, rows, row_start, seed, step, mode, chain, planes=None):
         """mean |F(v) - F(v')| of rows [row_start, +rows) of v, v' a fresh one-step reconstruction (rbm.py:225-233), in ONE

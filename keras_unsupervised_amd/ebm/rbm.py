@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from . import dp
+from . import ais, dp
 from .engine import (CHAIN_BH, CHAIN_BV, CHAIN_SCORE, CHAIN_STRIDE, CHAIN_W, MODE_COMPLEX,
                      MODE_VISIBLE_BERNOULLI, MODE_VISIBLE_GAUSSIAN, STREAM_INV_TRANSFORM, STREAM_TRANSFORM,
                      DeviceMatrix, DeviceRBM, device_guard, hidden_site, resolve_device, visible_site)
@@ -134,6 +134,8 @@ class RBM(object):
         self._epochs_done = 0          # epochs this object has trained: the index into a momentum schedule
         self._mom_kw = {}              # the `momentum=` keyword of this epoch's engine calls; empty with both terms 0
         self.last_scores = []
+        self.last_ais = None           # what the last log_partition() found (and the update count it was valid at)
+        self._ais_at = -1
 
     # ------------------------------------------------------------------ build ----------
     def build(self, input_shape):
@@ -286,6 +288,80 @@ class RBM(object):
 
     def compute_output_shape(self, input_shape):
         return (input_shape[0], self.output_dim)          # rbm.py:94-95
+
+    # ------------------------------------------------------------------ likelihood -------
+    def _check_likelihood(self, what):
+        if self.mode != MODE_VISIBLE_BERNOULLI:
+            raise ValueError("%s is defined for MODE_VISIBLE_BERNOULLI only: in MODE_VISIBLE_GAUSSIAN the hidden site is a "
+                             "thresholded relu (rbm.py:58-59), not the Bernoulli unit of an energy model this estimator is valid for"
+                             % what)
+
+    def _check_built(self, what):
+        if not self.built:
+            raise ValueError("%s needs a built RBM (call build / fit / transform first)" % what)
+
+    def log_partition(self, n_chains=512, betas=1000, base_rates=None, seed=None, method="ais"):
+        """log Z of the model (extension; the reference has no likelihood estimate).
+
+        method 'ais': annealed importance sampling (Salakhutdinov & Murray 2008) from the base-rate model to this one, n_chains
+        chains on the device in one library call (kurbm_ais_run).  betas: the number of annealing steps of a linear schedule, or
+        the schedule itself (0 ... 1, strictly increasing; ais.beta_schedule(n, 'three_stage') is the paper's).  base_rates: None
+        (b_A = 0: the uniform base model), a data matrix [rows, n_vis] (-> ais.base_rate_bias, the usual choice for a trained
+        model) or a bias vector [n_vis].  seed: of the chains' draws (default: the RBM's).
+        method 'exact': enumeration (ais.exact_log_partition; at most 24 units on the smaller side).
+        Returns a float and fills self.last_ais = {log_z, stderr, log_z0, logw, n_chains, n_betas}.  The fit / transform counters
+        and the weights are not touched."""
+        self._check_likelihood("log_partition")
+        if method not in ("ais", "exact"):
+            raise ValueError("method must be 'ais' or 'exact', got %r" % (method,))
+        if method == "ais":          # (arguments first: a bad schedule is refused whether or not the RBM is built)
+            if isinstance(betas, (int, np.integer)) and not isinstance(betas, bool):
+                if betas < 1:
+                    raise ValueError("betas: a schedule needs at least one step, got %d" % betas)
+                betas = ais.beta_schedule(int(betas))
+            else:
+                betas = ais.check_schedule(betas)
+            n_chains = int(n_chains)
+            if n_chains < 1:
+                raise ValueError("n_chains must be positive")
+        self._check_built("log_partition")
+        if method == "exact":
+            W, b_h, b_v = self._dev.get_weights()
+            log_z = ais.exact_log_partition(W, b_h, b_v)
+            self.last_ais = {"log_z": log_z, "stderr": 0.0, "log_z0": None, "logw": None, "n_chains": 0, "n_betas": 0}
+            self._ais_at = self._update_count
+            return log_z
+        d = self._dev
+        if base_rates is None:
+            b_a = np.zeros(d.n_vis, np.float64)
+        else:
+            b_a = np.asarray(base_rates, dtype=np.float64)
+            b_a = ais.base_rate_bias(b_a) if b_a.ndim == 2 else b_a.reshape(-1)
+            if b_a.size != d.n_vis:
+                raise ValueError("base_rates has %d columns, the RBM has %d visible units" % (b_a.size, d.n_vis))
+        b_a = b_a.astype(np.float32)          # what the device anneals from; log Z_0 is of exactly these values
+        logw, _ = d.ais_run(betas, n_chains, base_bias=b_a, seed=self.seed if seed is None else int(seed))
+        logw = logw.cpu().numpy()
+        log_z, stderr, z0 = ais.estimate(logw, b_a, d.n_hid)
+        self.last_ais = {"log_z": log_z, "stderr": stderr, "log_z0": z0, "logw": logw, "n_chains": n_chains, "n_betas": int(betas.size)}
+        self._ais_at = self._update_count
+        return log_z
+
+    def log_likelihood(self, V, log_z=None, **ais_kwargs):
+        """Mean log p(v) = -F(v) - log Z over the rows of V.  log_z: given, else the one log_partition cached (self.last_ais; a
+        fit() since then discards it), else log_partition(**ais_kwargs) is run first.  F(v) is cal_free_energy's device path."""
+        self._check_likelihood("log_likelihood")
+        if log_z is None:
+            cached = self.last_ais is not None and self._ais_at == self._update_count and not ais_kwargs
+            log_z = self.last_ais["log_z"] if cached else self.log_partition(**ais_kwargs)
+        self._check_built("log_likelihood")
+        x, _ = self._as_device(V)
+        if x.cols != self._dev.n_vis:
+            raise ValueError("V has %d columns, the RBM has %d visible units" % (x.cols, self._dev.n_vis))
+        if x.rows == 0:
+            raise ValueError("log_likelihood of an empty matrix")
+        F = self._dev.free_energy(x, x.rows, compute="x3" if self._large(x.rows) else None)
+        return float(-F.double().mean().item() - float(log_z))
 
     # ------------------------------------------------------------------ training --------
     def _score(self, Vd, lo, rows, step):
