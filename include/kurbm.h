@@ -553,6 +553,38 @@ int kurbm_ais_step(kurbm_ctx* ctx, const kurbm_params* p, const float* base_bias
                    float* h, int ldh, float* v_out, int ldvo, float* prob_h, float* u_h, float* prob_v, float* u_v,
                    void* ws, size_t ws_bytes, kurbm_stream_t stream);
 
+/*
+ * Gibbs runs: samples from a trained RBM (fantasy particles, conditional completions), both visible modes.  An extension: the
+ * reference offers one half step per call (transform_func / inv_transform_func, rbm.py:46-54, :58-67) and no clamping.
+ * From v_0 = v_init, sweep t = 1 .. T, T = burn_in + (n_keep - 1) * thin:
+ *     h_t = draw(p(h | v_{t-1})),   v_t = draw(p(v | h_t)),   then v_t[:, c] = v_init[:, c] for every clamped unit c.
+ * The sites are those of the half steps for `mode`: Bernoulli visibles h = [u < sigmoid(v.W + b_h)], v = [u < sigmoid(h.W^T + b_v)];
+ * Gaussian visibles h = [u < relu(v.W + b_h)], v = (h.W^T + b_v) + z.  Draws follow the Philox contract above with
+ * row = chain0 + chain, col = unit, step = t and the two stream ids below; chain0 % 4 == 0.
+ * Kept sample j (0 <= j < n_keep) is v_{burn_in + j * thin}, written to v_out + j * keep_stride as fp32 [n_chains][ldo];
+ * prob_out (nullable, same layout) receives the activated value it was drawn from -- the probability of Bernoulli visibles, the
+ * mean of Gaussian ones.  Clamped columns hold v_init's value in both.  burn_in, thin, n_keep >= 1.
+ * v_pieces describes v_init as for kurbm_cd_step_x3 (1 | KURBM_V_BINARY: every element 0.0 or 1.0; 1: exactly bf16; 3: any fp32).
+ * clamp (nullable) is a DEVICE array of n_vis bytes, non-zero = clamped; it is read by the run's launches, not by the host.
+ * One sweep is the two x3 half-step launches (bf16 matrix cores, products exact, fp32 accumulation); the states never leave their
+ * operand format -- byte planes for 0/1 states, three bf16 pieces for Gaussian visibles -- and only kept sweeps write fp32 planes.
+ * A mask adds one small launch per sweep (and one per run that lays the mask out in the planes' order).  Nothing is read back,
+ * nothing synchronises, the library allocates nothing.  The same call twice gives identical bits.  A chain's numbers are NOT
+ * promised to be independent of n_chains: the planner picks the tile shape by the row count, and with it the order of the fp32
+ * additions (the uniforms of a chain are the same whatever the count).
+ * Padding columns [n_vis, ld) of v_init are not read into a result; those of v_out / prob_out are not written.
+ * KURBM_ERR_ARG / KURBM_ERR_WORKSPACE, before anything is enqueued: a null or misaligned buffer, ld < n_vis or ld % 4 != 0,
+ * keep_stride < n_chains * ldo (or not a multiple of 4) when n_keep > 1, a count below 1, chain0 & 3, an unknown v_pieces or mode,
+ * mirror_bytes < kurbm_x3_mirror_bytes, ws_bytes < kurbm_gibbs_workspace_bytes (0 for a bad shape).  The mirror is the x3 mirror.
+ */
+#define KURBM_STREAM_GIBBS_H 0x210u
+#define KURBM_STREAM_GIBBS_V 0x211u   /* Gaussian visibles: normals from this plane and | 0x80000000, as everywhere */
+size_t kurbm_gibbs_workspace_bytes(kurbm_ctx* ctx, int n_chains, int n_vis, int n_hid, int v_pieces, int mode);
+int kurbm_gibbs_run(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t mirror_bytes, const float* v_init, int v_pieces,
+                    int ldv, int n_chains, uint64_t chain0, uint64_t seed, int mode, int burn_in, int thin, int n_keep,
+                    const uint8_t* clamp, float* v_out, float* prob_out, int ldo, size_t keep_stride, void* ws, size_t ws_bytes,
+                    kurbm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -120,6 +120,10 @@ SIGNATURES = {
     "kurbm_ais_run": (_i, [_vp, _PP, _vp, C.POINTER(C.c_double), _i, _i, C.c_uint64, C.c_uint64, _vp, _vp, _i, _vp, _sz, _vp]),
     "kurbm_ais_step": (_i, [_vp, _PP, _vp, C.c_double, C.c_double, _i, _vp, _i, _i, C.c_uint64, C.c_uint64, _vp, _vp, _i, _vp, _i,
                             _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # Gibbs runs: clamp is a DEVICE array of n_vis bytes (nullable)
+    "kurbm_gibbs_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
+    "kurbm_gibbs_run": (_i, [_vp, _PP, _vp, _sz, _vp, _i, _i, _i, C.c_uint64, C.c_uint64, _i, _i, _i, _i, _vp, _vp, _vp, _i, _sz,
+                             _vp, _sz, _vp]),
 }
 
 ABI_VERSION = 5

@@ -1549,6 +1549,133 @@ static int cd_step_any(kurbm_ctx* ctx, int pieces, int v_pieces, const kurbm_par
     return KURBM_OK;
 }
 
+// ---- Gibbs runs (include/kurbm.h: kurbm_gibbs_run) -------------------------------------------------------------------------
+// Workspace of a run on `rows` chains: the converted start plane v0 (kept for the whole run: clamped units are copied back from
+// it), the current visible plane vc, the hidden plane hb, and the clamp mask in the order of a plane row's positions.  Formats:
+//   Gaussian visibles    v0 and vc are three bf16 pieces (a start that is exactly bf16 has zero mid / lo pieces);
+//   Bernoulli, 0/1 start v0 and vc are k-permuted byte planes (one bf16 piece with KURBM_X3_BYTES = 0);
+//   Bernoulli, real start (v_pieces 1 or 3): v0 is v_pieces bf16 pieces; vc is a byte plane -- unless units are clamped: the
+//                        clamped values are real, so vc then keeps v0's format (its 0/1 samples have zero mid / lo pieces).
+// The size does not depend on whether a mask is given: vc is carved for the larger case.
+struct GibbsWorkspace {
+    uint16_t *v0, *vc, *hb;
+    unsigned char* maskp;
+    int Kv, Kh, Kb, Lv, Lh, sp, cp;
+    bool sbytes, cbytes, hbytes;
+    size_t planeV, bytes;
+};
+static GibbsWorkspace carve_gibbs(const kurbm_ctx* ctx, void* base, int rows, int n_vis, int n_hid, int v_pieces, int mode, bool clamp) {
+    GibbsWorkspace w;
+    const bool gauss = mode == KURBM_MODE_VISIBLE_GAUSSIAN, v_binary = v_pieces == (1 | KURBM_V_BINARY);
+    const int vp = v_binary ? 1 : v_pieces;
+    const bool byt = ctx->knob[KN_X3_BYTES] != 0;
+    w.hbytes = byt;
+    if (gauss) { w.sp = w.cp = 3; w.sbytes = w.cbytes = false; }
+    else {
+        w.sp = vp; w.sbytes = byt && v_binary;
+        if (w.sbytes) { w.cp = 1; w.cbytes = true; }
+        else if (clamp) { w.cp = w.sp; w.cbytes = false; }
+        else { w.cp = 1; w.cbytes = byt; }
+    }
+    w.Kv = round_up(n_vis, 128); w.Kh = round_up(n_hid, 128); w.Kb = round_up(rows, 128);
+    w.Lv = ld_pad(ctx, w.Kv); w.Lh = ld_pad(ctx, w.Kh);
+    w.planeV = (size_t)w.Kb * w.Lv;
+    char* b = static_cast<char*>(base);
+    size_t off = 0;
+    auto take16 = [&](size_t n) { uint16_t* p = reinterpret_cast<uint16_t*>(b + off); off = align_up(off + n * 2); return p; };
+    w.v0 = take16(w.sp * w.planeV);
+    w.vc = take16((gauss ? 3 : vp) * w.planeV);
+    w.hb = take16((size_t)w.Kb * w.Lh);
+    w.maskp = reinterpret_cast<unsigned char*>(b + off); off = align_up(off + (size_t)w.Kv);
+    w.bytes = off;
+    return w;
+}
+
+static bool gibbs_shape_ok(int n_chains, int v_pieces, int mode) {
+    return n_chains > 0 && (v_pieces == 1 || v_pieces == 3 || v_pieces == (1 | KURBM_V_BINARY)) &&
+           (mode == KURBM_MODE_VISIBLE_BERNOULLI || mode == KURBM_MODE_VISIBLE_GAUSSIAN);
+}
+
+extern "C" {
+
+size_t kurbm_gibbs_workspace_bytes(kurbm_ctx* ctx, int n_chains, int n_vis, int n_hid, int v_pieces, int mode) {
+    if (!ctx || n_vis <= 0 || n_hid <= 0 || !gibbs_shape_ok(n_chains, v_pieces, mode)) return 0;
+    return carve_gibbs(ctx, nullptr, n_chains, n_vis, n_hid, v_pieces, mode, false).bytes;
+}
+
+int kurbm_gibbs_run(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t mirror_bytes, const float* v_init, int v_pieces,
+                    int ldv, int n_chains, uint64_t chain0, uint64_t seed, int mode, int burn_in, int thin, int n_keep,
+                    const uint8_t* clamp, float* v_out, float* prob_out, int ldo, size_t keep_stride, void* ws, size_t ws_bytes,
+                    kurbm_stream_t stream) {
+    // every check before the first launch: a refused call has written nothing
+    if (!ctx) return fail(KURBM_ERR_ARG, "ctx is null");
+    if (int e = check_params(p)) return e;
+    if (n_chains <= 0) return fail(KURBM_ERR_ARG, "n_chains must be positive");
+    if (mode != KURBM_MODE_VISIBLE_BERNOULLI && mode != KURBM_MODE_VISIBLE_GAUSSIAN) return fail(KURBM_ERR_ARG, "unknown mode %d", mode);
+    if (!gibbs_shape_ok(n_chains, v_pieces, mode)) return fail(KURBM_ERR_ARG, "v_pieces must be 1, 1 | KURBM_V_BINARY or 3");
+    if (burn_in < 1 || thin < 1 || n_keep < 1) return fail(KURBM_ERR_ARG, "burn_in, thin and n_keep must be >= 1");
+    const long long T = (long long)burn_in + (long long)(n_keep - 1) * thin;
+    if (T > 0x7FFFFFFFll) return fail(KURBM_ERR_ARG, "burn_in + (n_keep - 1) * thin exceeds 2^31 - 1 sweeps");
+    if (chain0 & 3) return fail(KURBM_ERR_ARG, "chain0 must be a multiple of 4");
+    if (bad_matrix(v_init, ldv, p->n_vis)) return fail(KURBM_ERR_ARG, "v_init: null, misaligned, ld %% 4 != 0 or ld < n_vis");
+    if (bad_matrix(v_out, ldo, p->n_vis)) return fail(KURBM_ERR_ARG, "v_out: null, misaligned, ld %% 4 != 0 or ld < n_vis");
+    if (prob_out && !aligned16(prob_out)) return fail(KURBM_ERR_ARG, "prob_out is misaligned");
+    if (n_keep > 1 && (keep_stride < (size_t)n_chains * (size_t)ldo || keep_stride % 4 != 0))
+        return fail(KURBM_ERR_ARG, "keep_stride below n_chains * ldo floats, or not a multiple of 4");
+    if (!mirror || !ws || !aligned16(mirror) || !aligned16(ws)) return fail(KURBM_ERR_ARG, "mirror/workspace null or misaligned");
+    const Mirror m = carve_mirror(ctx, mirror, p->n_vis, p->n_hid, 3);
+    if (m.bytes > mirror_bytes) return fail(KURBM_ERR_WORKSPACE, "mirror too small: need %zu bytes, got %zu", m.bytes, mirror_bytes);
+    const size_t need = carve_gibbs(ctx, nullptr, n_chains, p->n_vis, p->n_hid, v_pieces, mode, false).bytes;
+    if (need > ws_bytes) return fail(KURBM_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
+    const GibbsWorkspace w = carve_gibbs(ctx, ws, n_chains, p->n_vis, p->n_hid, v_pieces, mode, clamp != nullptr);
+    if (clamp && ((size_t)w.Lv * (w.cbytes ? 1 : 2)) % 16 != 0)
+        return fail(KURBM_ERR_UNSUPPORTED, "clamping needs plane rows of whole 16-byte groups (KURBM_LDPAD = %d)", ctx->knob[KN_LDPAD]);
+
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool gauss = mode == KURBM_MODE_VISIBLE_GAUSSIAN;
+    const int act_h = gauss ? ACT_RELU : ACT_SIGMOID, act_v = gauss ? ACT_LINEAR : ACT_SIGMOID;
+    const int noise_v = gauss ? NOISE_GAUSSIAN : NOISE_BERNOULLI;
+    // the start plane, converted once; with a mask, the current plane starts as its copy (same format) so that every sweep reads vc
+    HIP_TRY(launch_f32_to_bf16(v_init, n_chains, p->n_vis, ldv, w.v0, w.Lv, w.Kb, nullptr, 0, 0, w.sp, w.planeV, 0, nullptr, 0, st,
+                               0, w.sbytes ? 1 : 0));
+    if (clamp) HIP_TRY(launch_gibbs_mask(clamp, p->n_vis, w.maskp, w.Kv, w.cbytes ? 1 : 0, st));
+    int e;
+    for (long long t = 1; t <= T; ++t) {
+        const bool first = t == 1;
+        const long long since = t - burn_in;
+        const bool kept = since >= 0 && since % thin == 0;
+        const size_t joff = kept ? (size_t)(since / thin) * keep_stride : 0;
+        RngArgs r = make_rng(seed, chain0, KURBM_STREAM_GIBBS_H, (uint32_t)t);          // h_t ~ p(h | v_{t-1})
+        {
+            HalfOutB ho;
+            ho.out = w.hb; ho.ldo = w.Lh; ho.out_bytes = w.hbytes;
+            if ((e = half_step_b(ctx, LAYOUT_VH, p, m, first ? w.v0 : w.vc, w.Lv, first ? w.sp : w.cp, w.planeV, n_chains, act_h,
+                                 NOISE_BERNOULLI, &r, ho, st, first ? w.sbytes : w.cbytes)))
+                return e;
+        }
+        r = make_rng(seed, chain0, KURBM_STREAM_GIBBS_V, (uint32_t)t);                  // v_t ~ p(v | h_t)
+        {
+            HalfOutB ho;
+            ho.out = w.vc; ho.ldo = w.Lv; ho.out_pieces = w.cp; ho.out_plane = w.planeV; ho.out_bytes = w.cbytes;
+            if (kept) { ho.out_f32 = v_out + joff; ho.prob_f32 = prob_out ? prob_out + joff : nullptr; ho.ldo32 = ldo; }
+            if ((e = half_step_b(ctx, LAYOUT_HV, p, m, w.hb, w.Lh, 1, 0, n_chains, act_v, noise_v, &r, ho, st, w.hbytes))) return e;
+        }
+        if (clamp) {   // v_t[:, c] = v_init[:, c]: the plane the next sweep reads and, on a kept sweep, the fp32 planes just written
+            GibbsClampArgs a;
+            memset(static_cast<void*>(&a), 0, sizeof a);
+            a.cur = reinterpret_cast<unsigned char*>(w.vc); a.start = reinterpret_cast<const unsigned char*>(w.v0); a.maskp = w.maskp;
+            a.rows = n_chains; a.ngroups = w.Kv / 8; a.es = w.cbytes ? 1 : 2; a.pieces = w.cp; a.perm = w.cbytes ? 1 : 0;
+            a.n_vis = p->n_vis;
+            a.ld_bytes = (size_t)w.Lv * a.es; a.plane_bytes = w.planeV * 2;
+            if (kept) { a.v_init = v_init; a.ldv = ldv; a.v_out = v_out + joff; a.prob_out = prob_out ? prob_out + joff : nullptr; a.ldo = ldo; }
+            HIP_TRY(launch_gibbs_clamp(a, st));
+        }
+    }
+    return KURBM_OK;
+}
+
+}  // extern "C"
+
 extern "C" {
 
 size_t kurbm_bf16_mirror_bytes(kurbm_ctx* ctx, int n_vis, int n_hid) {

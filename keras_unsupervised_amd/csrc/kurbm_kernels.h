@@ -86,6 +86,22 @@ hipError_t launch_ais_start(float* v, int ldv, const float* b_v, const float* ba
 hipError_t launch_ais_accumulate(const float* sppart, int ng_sp, const float* vpart, int ng_v, int ld_part, float dbeta,
                                  double* logw, float* dlogw, int rows, hipStream_t st);
 
+// kurbm_gibbs.hip: the small launches of a Gibbs run (kurbm_gibbs_run) around the x3 half steps
+//   launch_gibbs_mask:  maskp[pos] = 0xFF where the unit stored at position `pos` of a plane row is clamped, else 0 (pos < npos,
+//                       npos % 8 == 0).  perm = 1: the plane is a k-permuted byte plane, position pos holds column kperm64^-1(pos).
+//   launch_gibbs_clamp: cur[row][pos] = start[row][pos] wherever maskp[pos] is set, for every piece of the plane (es bytes per
+//                       element: 1 = byte plane, 2 = bf16 pieces; both planes share ld_bytes and plane_bytes); with v_out / prob_out
+//                       (nullable) the same columns of those fp32 planes are rewritten from v_init.  One thread per 8 positions.
+struct GibbsClampArgs {
+    unsigned char* cur; const unsigned char* start; const unsigned char* maskp;
+    int rows, ngroups, es, pieces, perm, n_vis;
+    size_t ld_bytes, plane_bytes;
+    const float* v_init; int ldv;
+    float* v_out; float* prob_out; int ldo;
+};
+hipError_t launch_gibbs_mask(const unsigned char* clamp, int n_vis, unsigned char* maskp, int npos, int perm, hipStream_t st);
+hipError_t launch_gibbs_clamp(const GibbsClampArgs& a, hipStream_t st);
+
 // Diagnostic hook: the next GEMM launches write their s_memtime stamps here (null = off).
 void set_stamp_buffer(unsigned long long* p);
 void set_debug_off(int mask);

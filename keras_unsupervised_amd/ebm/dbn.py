@@ -75,3 +75,38 @@ class DBN(object):
         for rbm_layer in reversed(layers):
             H_p = rbm_layer.inv_transform(H_p)
         return layers[0]._ret(H_p, kind, False)
+
+    def transform_probs(self, V):
+        """Chain of layer.hidden_probs: the deterministic (mean-field) features of V, no draw anywhere (extension)."""
+        layers = self._layers()
+        V_p, kind = self._to_device(layers[0], V)
+        for rbm_layer in layers:
+            V_p = rbm_layer.hidden_probs(V_p)
+        return layers[0]._ret(V_p, kind, False)
+
+    def sample(self, n_samples, burn_in=1000, thin=100, n_chains=None, init=None, return_prob=False, seed=None):
+        """n_samples "dreams" of the network (extension), [n_samples, n_vis of the first layer]: a Gibbs run in the TOP RBM
+        (RBM.sample: burn_in, thin, n_chains, seed as there), then one ancestral pass down through inv_transform of the lower
+        layers, in the order of DBN.inv_transform.  init [n_chains, n_vis of the first layer] starts the top chains from its
+        sampled representation (layer.transform up to the top RBM's input).  return_prob: the bottom layer's visible_probs of the
+        last hidden states instead of its sample.  A host array, or where init came from."""
+        layers = self._layers()
+        if not all(layer.built for layer in layers):
+            raise ValueError("sample needs built RBM layers")
+        kind, top_init = "numpy", None
+        if init is not None:
+            top_init, kind = self._to_device(layers[0], init)
+            for rbm_layer in layers[:-1]:
+                top_init = rbm_layer.transform(top_init)
+        n_samples = int(n_samples)
+        H_p, _, _ = layers[-1]._sample(n_samples, n_chains, burn_in, thin, top_init, None, False, seed)
+        if H_p.rows != n_samples:                 # (kept, chain) order: the first n_samples rows
+            H_p = DeviceMatrix(H_p.t, n_samples, H_p.cols, H_p.ld)
+        if len(layers) == 1:
+            if return_prob:
+                raise ValueError("return_prob needs a layer below the top RBM (use RBM.sample(return_prob=True))")
+            return layers[0]._ret(H_p, kind, False)
+        for rbm_layer in reversed(layers[1:-1]):
+            H_p = rbm_layer.inv_transform(H_p)
+        H_p = layers[0].visible_probs(H_p) if return_prob else layers[0].inv_transform(H_p)
+        return layers[0]._ret(H_p, kind, False)

@@ -25,11 +25,33 @@ STREAM_INV_TRANSFORM = 0x101
 STREAM_AIS_INIT = 0x200
 STREAM_AIS_H = 0x201
 STREAM_AIS_V = 0x202
+# the two sites of a Gibbs run (kurbm_gibbs_run): h and v of sweep t (step t); row = the chain's index
+STREAM_GIBBS_H = 0x210
+STREAM_GIBBS_V = 0x211
 CHAIN_W, CHAIN_BH, CHAIN_BV, CHAIN_SCORE = 0, 1, 2, 3
 
 
 def round_up(x, m):
     return (x + m - 1) // m * m
+
+
+def clamp_mask(clamp, n_vis):
+    """A clamp argument as a host uint8 mask [n_vis] (1 = clamped): a BOOLEAN mask of that length, or a list of unit indices
+    (integers; an integer array is always read as indices)."""
+    a = clamp.detach().cpu().numpy() if isinstance(clamp, torch.Tensor) else np.asarray(clamp)
+    if a.dtype == np.bool_:
+        if a.shape != (n_vis,):
+            raise ValueError("clamp mask has shape %s, the RBM has %d visible units" % (a.shape, n_vis))
+        return np.ascontiguousarray(a != 0, dtype=np.uint8)
+    idx = a.reshape(-1)
+    if idx.size and idx.dtype.kind not in "iu":
+        raise ValueError("clamp must be a boolean mask [n_vis] or a list of unit indices")
+    idx = idx.astype(np.int64)
+    if idx.size and (idx.min() < 0 or idx.max() >= n_vis):
+        raise ValueError("clamp index out of range for %d visible units" % n_vis)
+    m = np.zeros(n_vis, np.uint8)
+    m[idx] = 1
+    return m
 
 
 def resolve_device(device=None):
@@ -690,6 +712,54 @@ class DeviceRBM:
                                           ptr("u_v"), ws.data_ptr(), ws.numel(), self._stream()))
         return out
 
+    # -- Gibbs runs (include/kurbm.h: kurbm_gibbs_run) ------------------------------------------
+    def gibbs_workspace(self, n_chains, v_pieces, mode):
+        n = int(self.lib.kurbm_gibbs_workspace_bytes(self.ctx.handle, int(n_chains), self.n_vis, self.n_hid, int(v_pieces), int(mode)))
+        if n == 0:
+            raise _lib.KurbmError("kurbm_gibbs_workspace_bytes failed")
+        return self._alloc_bytes(n, "gibbs_workspace", zero=False)
+
+    def _clamp_mask(self, clamp):
+        """The clamp mask as n_vis device bytes (non-zero = clamped): a uint8 device tensor as is; a boolean mask [n_vis] or a
+        list of unit indices uploaded; None stays None."""
+        if clamp is None:
+            return None
+        if isinstance(clamp, torch.Tensor) and clamp.dtype == torch.uint8 and clamp.device == self.device:
+            if clamp.numel() != self.n_vis:
+                raise ValueError("clamp has %d entries, the RBM has %d visible units" % (clamp.numel(), self.n_vis))
+            return clamp
+        t = self._alloc_bytes(self.n_vis, "clamp", zero=False)
+        t.copy_(torch.from_numpy(clamp_mask(clamp, self.n_vis)))
+        return t
+
+    def gibbs_run(self, v, burn_in=1, thin=1, n_keep=1, chain0=0, seed=0, mode=MODE_VISIBLE_BERNOULLI, clamp=None,
+                  want_prob=False, ws=None):
+        """Gibbs sweeps from the rows of DeviceMatrix v (one chain per row, global indices chain0 ...) in ONE library call: two
+        x3 half-step launches per sweep, the states kept in their operand format, nothing read back here.  Kept sample j is the
+        state after burn_in + j * thin sweeps.  clamp: see _clamp_mask; those units keep v's values.
+        Returns (samples, probs): DeviceMatrix [n_keep * rows, n_vis] in (kept, chain) order; probs (want_prob, else None) holds
+        the activated value each sample was drawn from."""
+        if v.cols != self.n_vis:
+            raise ValueError("input has %d columns, expected %d" % (v.cols, self.n_vis))
+        rows, n_keep = int(v.rows), int(n_keep)
+        if rows < 1:
+            raise ValueError("a Gibbs run needs at least one chain")
+        with torch.cuda.device(self.device):
+            vp = self._x3_pieces(v, None, mode)
+            mask = self._clamp_mask(clamp)
+            mir = self.mirror(3)
+            ws = self.gibbs_workspace(rows, vp, mode) if ws is None else ws
+            out = self._alloc_out(max(n_keep, 1) * rows, self.n_vis, "gibbs_v")
+            prob = self._alloc_out(max(n_keep, 1) * rows, self.n_vis, "gibbs_prob") if want_prob else None
+            check(self.lib.kurbm_gibbs_run(self.ctx.handle, C.byref(self.params), mir.data_ptr(), mir.numel(), v.ptr(), vp, v.ld,
+                                           rows, int(chain0), int(seed), int(mode), int(burn_in), int(thin), n_keep,
+                                           mask.data_ptr() if mask is not None else None, out.ptr(),
+                                           prob.ptr() if prob is not None else None, out.ld, rows * out.ld,
+                                           ws.data_ptr(), ws.numel(), self._stream()))
+            if mode == MODE_VISIBLE_BERNOULLI and mask is None:
+                out.bf16_exact = out.binary = True        # 0/1: one bf16 piece, no need to look
+        return out, prob
+
     def score_x3(self, v, rows, row_start, seed, step, mode, chain, planes=None):
         """mean |F(v) - F(v')| of rows [row_start, +rows) of v, v' a fresh one-step reconstruction (rbm.py:225-233), in ONE
         library call on the x3 kernels; returns a device tensor whose element 0 is the score -- nothing is read back here."""
@@ -762,4 +832,5 @@ def visible_site(mode):
 
 
 __all__ = ["DeviceRBM", "DeviceMatrix", "ResidentPlanes", "resolve_device", "device_guard", "hidden_site", "visible_site", "round_up",
+           "clamp_mask", "STREAM_GIBBS_H", "STREAM_GIBBS_V",
            "MODE_VISIBLE_BERNOULLI", "MODE_VISIBLE_GAUSSIAN", "MODE_COMPLEX", "NOISE_NONE"]

@@ -28,7 +28,7 @@ import torch
 from .. import _lib
 from . import ais, dp
 from .engine import (CHAIN_BH, CHAIN_BV, CHAIN_SCORE, CHAIN_STRIDE, CHAIN_W, MODE_COMPLEX,
-                     MODE_VISIBLE_BERNOULLI, MODE_VISIBLE_GAUSSIAN, STREAM_INV_TRANSFORM, STREAM_TRANSFORM,
+                     MODE_VISIBLE_BERNOULLI, MODE_VISIBLE_GAUSSIAN, STREAM_GIBBS_V, STREAM_INV_TRANSFORM, STREAM_TRANSFORM,
                      DeviceMatrix, DeviceRBM, device_guard, hidden_site, resolve_device, visible_site)
 
 _UPDATE_MODES = ("fused", "reference_sequential")
@@ -136,6 +136,7 @@ class RBM(object):
         self.last_scores = []
         self.last_ais = None           # what the last log_partition() found (and the update count it was valid at)
         self._ais_at = -1
+        self._chains_used = 0          # Gibbs chains handed out by gibbs() / sample() so far (a multiple of 4): their chain0
 
     # ------------------------------------------------------------------ build ----------
     def build(self, input_shape):
@@ -362,6 +363,114 @@ class RBM(object):
             raise ValueError("log_likelihood of an empty matrix")
         F = self._dev.free_energy(x, x.rows, compute="x3" if self._large(x.rows) else None)
         return float(-F.double().mean().item() - float(log_z))
+
+    # ------------------------------------------------------------------ sampling ---------
+    def _take_chains(self, n):
+        """Fresh chain indices for n chains: the count handed out so far (kept a multiple of 4, as the draws' row0 must be)."""
+        chain0 = self._chains_used
+        self._chains_used = (chain0 + int(n) + 3) // 4 * 4
+        return chain0
+
+    def _gibbs_out(self, out, prob, n_rows, kind, return_prob):
+        cut = lambda m: m if m.rows == n_rows else DeviceMatrix(m.t, n_rows, m.cols, m.ld)
+        v = self._ret(cut(out), kind, False)
+        return (v, self._ret(cut(prob), kind, False)) if return_prob else v
+
+    def gibbs(self, v, n_steps=1, clamp=None, return_prob=False, seed=None):
+        """The chains after n_steps Gibbs sweeps from the rows of v (extension; the reference has one half step per call):
+        h ~ p(h | v), v ~ p(v | h) at the sites of transform / inv_transform for this mode, in ONE library call
+        (kurbm_gibbs_run).  clamp: a boolean mask [n_vis] or a list of unit indices -- those units keep v's values (a
+        conditional completion).  return_prob: also the probabilities (Gaussian visibles: the means) the last states were drawn
+        from, as (samples, probs).  seed: of the draws (default: the RBM's).  Every call takes fresh chain indices, so two calls
+        never reuse draws, and a run is reproducible from (seed, the number of chains handed out before it).  The fit / transform
+        counters, the weights and the cached AIS result are not touched.  Results go back where v came from, as one array."""
+        self._check_built("gibbs")
+        n_steps = int(n_steps)
+        if n_steps < 1:
+            raise ValueError("n_steps must be >= 1")
+        x, kind = self._as_device(v)
+        d = self._dev
+        if x.cols != d.n_vis:
+            raise ValueError("v has %d columns, the RBM has %d visible units" % (x.cols, d.n_vis))
+        if x.rows == 0:
+            raise ValueError("gibbs on an empty matrix")
+        out, prob = d.gibbs_run(x, burn_in=n_steps, thin=1, n_keep=1, chain0=self._take_chains(x.rows),
+                                seed=self.seed if seed is None else int(seed), mode=self.mode, clamp=clamp,
+                                want_prob=bool(return_prob))
+        return self._gibbs_out(out, prob, x.rows, kind, return_prob)
+
+    def _start_chains(self, n_chains, chain0, seed):
+        """v_0 of fresh chains: [u < sigmoid(b_v)] (Bernoulli visibles; u = the Philox uniforms of site STREAM_GIBBS_V at step 0,
+        the sweep before the first) or b_v itself (Gaussian visibles).  Elementwise device arithmetic; no kernel of its own."""
+        d = self._dev
+        with device_guard(d.device):
+            m = DeviceMatrix.zeros(n_chains, d.n_vis, d.device)
+            if self.mode == MODE_VISIBLE_GAUSSIAN:
+                m.view().copy_(d.b_v.reshape(1, -1).expand(n_chains, d.n_vis))
+            else:
+                u = d.philox_uniform(n_chains, d.n_vis, seed, STREAM_GIBBS_V, 0, row0=chain0)
+                m.view().copy_((u.view() < torch.sigmoid(d.b_v).reshape(1, -1)).to(torch.float32))
+                m.bf16_exact = m.binary = True
+        return m
+
+    def sample(self, n_samples, n_chains=None, burn_in=1000, thin=100, init=None, clamp=None, return_prob=False, seed=None):
+        """n_samples draws from the model by Gibbs sampling (extension), [n_samples, n_vis].  n_chains (default n_samples:
+        independent chains, one kept sample each) chains run burn_in sweeps; with fewer chains each keeps ceil(n_samples /
+        n_chains) states `thin` sweeps apart, and the first n_samples rows in (kept, chain) order are returned.  init: the chains'
+        start [n_chains, n_vis]; None starts them at [u < sigmoid(b_v)] (Bernoulli visibles) or b_v (Gaussian).  clamp (mask or
+        index list, see gibbs) needs init, which carries the clamped values.  return_prob, seed, the chain bookkeeping and what
+        is left untouched: as gibbs.  The result is a host array, or goes where init came from."""
+        out, prob, kind = self._sample(n_samples, n_chains, burn_in, thin, init, clamp, return_prob, seed)
+        return self._gibbs_out(out, prob, int(n_samples), kind, return_prob)
+
+    def _sample(self, n_samples, n_chains, burn_in, thin, init, clamp, return_prob, seed):
+        """sample() up to the device results: (samples, probs or None -- DeviceMatrix [n_keep * n_chains, n_vis] -- and where
+        init came from).  DBN.sample takes the top RBM's states from here without a trip through the host."""
+        self._check_built("sample")
+        n_samples = int(n_samples)
+        n_chains = n_samples if n_chains is None else int(n_chains)
+        burn_in, thin = int(burn_in), int(thin)
+        if n_samples < 1 or n_chains < 1:
+            raise ValueError("n_samples and n_chains must be positive")
+        if burn_in < 1 or thin < 1:
+            raise ValueError("burn_in and thin must be >= 1")
+        if clamp is not None and init is None:
+            raise ValueError("clamp needs init: it carries the clamped values")
+        d = self._dev
+        seed = self.seed if seed is None else int(seed)
+        kind = "numpy"
+        if init is not None:
+            x, kind = self._as_device(init)
+            if x.cols != d.n_vis or x.rows != n_chains:
+                raise ValueError("init has shape (%d, %d), expected (%d, %d)" % (x.rows, x.cols, n_chains, d.n_vis))
+        chain0 = self._take_chains(n_chains)
+        if init is None:
+            x = self._start_chains(n_chains, chain0, seed)
+        n_keep = -(-n_samples // n_chains)
+        out, prob = d.gibbs_run(x, burn_in=burn_in, thin=thin, n_keep=n_keep, chain0=chain0, seed=seed, mode=self.mode,
+                                clamp=clamp, want_prob=bool(return_prob))
+        return out, prob, kind
+
+    def _probs(self, direction, x, act):
+        d = self._dev
+        if x.rows == 0:
+            return DeviceMatrix.zeros(0, d.n_hid if direction == "vh" else d.n_vis, d.device)
+        if self._large(x.rows):
+            return d.half_step_bf16(direction, x, x.rows, act, _lib.NOISE_NONE, 0, 0, 0, pieces=3, want_prob=True, want_u=False)["prob"]
+        return d.half_step(direction, x, x.rows, 0, act, _lib.NOISE_NONE, 0, 0, 0, want_sample=False, want_prob=True)["prob"]
+
+    def hidden_probs(self, v):
+        """The activated hidden values of v without a draw -- sigmoid(v.W + b_h), or relu(v.W + b_h) with Gaussian visibles: the
+        deterministic counterpart of transform (mean-field features).  No RNG counter is consumed.  One array, where v came from."""
+        self._ensure_built(self._n_cols(v))
+        x, kind = self._as_device(v)
+        return self._ret(self._probs("vh", x, hidden_site(self.mode)[0]), kind, False)
+
+    def visible_probs(self, h):
+        """The activated visible values of h without a draw -- sigmoid(h.W^T + b_v), or the mean h.W^T + b_v of Gaussian visibles."""
+        self._check_built("visible_probs")
+        x, kind = self._as_device(h)
+        return self._ret(self._probs("hv", x, visible_site(self.mode)[0]), kind, False)
 
     # ------------------------------------------------------------------ training --------
     def _score(self, Vd, lo, rows, step):
