@@ -585,6 +585,51 @@ int kurbm_gibbs_run(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t 
                     const uint8_t* clamp, float* v_out, float* prob_out, int ldo, size_t keep_stride, void* ws, size_t ws_bytes,
                     kurbm_stream_t stream);
 
+/*
+ * Softmax label units: joint training on [pixels | one-hot label], exact class posteriors.  An extension: the reference's only road
+ * from an RBM to a class is a separate softmax head on sampled features (examples/rbm/rbm_softmax_mnist.py).
+ * A label RBM has n_vis = n_pix + C visible units, 2 <= C = n_labels <= 64; the LAST C columns are the label block -- rows
+ * n_pix .. n_vis-1 of W, entries n_pix .. n_vis-1 of b_v.  Bernoulli visibles only.  Exactly one unit of the block is on.
+ *   Label site, given the hidden states h of a row:
+ *     x_c = b_v[n_pix + c] + sum_j h_j W[n_pix + c][j];   p = softmax(x) in fp32: subtract the max, exp, sum in class order, divide;
+ *     u = u(row, col = n_pix) under the Philox contract above -- ONE uniform per row, stream id and step those of the h -> v site
+ *     the block belongs to (chain*64 + 2t-1 inside a CD step);  the drawn class is the first c with u < p_0 + ... + p_c (running
+ *     fp32 sum in class order), else C-1;  the block becomes that one-hot vector.  A row's p and draw do not depend on how many
+ *     rows share the launch; every reduction order is fixed and nothing is atomic.
+ *   Class logits, for pixels v (any real values), a = v.W[:n_pix] + b_h:
+ *     logit_c = b_v[n_pix + c] + sum_j softplus(a_j + W[n_pix + c][j])      (the overflow-free softplus of kurbm_free_energy)
+ *     p(y = c | v) = softmax_c(logit);   F(v, y = c) = -v.b_v[:n_pix] - logit_c.
+ *   CD step with labels = kurbm_cd_step on the n_vis-wide batch, except that after EVERY h -> v half step the block of that v_t is
+ *     rewritten by the label site (so a persistent chain keeps one-hot blocks), and for the last v_t the label columns of the
+ *     visible-bias sums become sum_rows(v_batch - v_neg) over the new block; h_neg, the statistics and the apply see that v_neg.
+ *     The positive phase and the v -> h half steps need nothing: a one-hot block is 0/1 columns.
+ * The x3 / bf16 / one-launch paths have no label site: a label RBM trains on the fp32 five-launch path.
+ * KURBM_ERR_ARG, before anything is enqueued, for n_labels outside [2, 64] or >= n_vis, a mode other than Bernoulli, and whatever
+ * the plain twin refuses; KURBM_ERR_WORKSPACE for a short workspace.
+ *
+ * kurbm_label_sample: the label site alone (test hook; the host's inv_transform).  h [rows][ldh] fp32 (read as real values); the
+ * label columns of v [rows][ldv] are written as fp32 0/1 -- its pixel and padding columns are neither read nor written; prob
+ * (nullable) [rows][ldp] receives p, out_u (nullable) [rows] the uniforms.  rng->row0 % 4 == 0.
+ */
+int kurbm_label_sample(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* h, int rows, int ldh,
+                       const kurbm_rng* rng, float* v, int ldv, float* prob, int ldp, float* out_u, kurbm_stream_t stream);
+/* kurbm_cd_step / kurbm_cd_step_mom (mom null / not null) and kurbm_cd_epoch / kurbm_cd_epoch_mom with the label site: the fp32
+ * launches of the plain step plus one small launch per h -> v half step.  k, v_chain, apply, delta_out, which, row0, chain and
+ * mom are honoured exactly as there; the workspace is that of kurbm_workspace_bytes (with its ldv addition), nothing more. */
+int kurbm_cd_step_labels(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* v_batch, int rows, int ldv,
+                         const kurbm_cd_opts* opts, int which, void* workspace, size_t workspace_bytes, kurbm_stream_t stream,
+                         const kurbm_momentum* mom /* nullable */);
+int kurbm_cd_epoch_labels(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* V, int n_rows, int ldv, int batch_size,
+                          const kurbm_cd_opts* opts, void* workspace, size_t workspace_bytes, kurbm_stream_t stream,
+                          const kurbm_momentum* mom /* nullable */);
+/* Class logits [rows][ldl] and, nullable, their softmax prob [rows][ldl] (same leading dimension) in two launches: the linear
+ * v -> h half step on the pixel rows of W (they are its top rows: nothing is copied) into the workspace, then one launch that reads
+ * that plane once with all C classes in registers.  v needs only n_pix valid columns (ldv >= n_pix); a label block behind them is
+ * ignored.  Workspace: kurbm_class_workspace_bytes (0 for a bad shape). */
+size_t kurbm_class_workspace_bytes(kurbm_ctx* ctx, int rows, int n_vis, int n_hid);
+int kurbm_class_logits(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* v, int rows, int ldv, float* logits,
+                       int ldl, float* prob, void* workspace, size_t workspace_bytes, kurbm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -124,6 +124,12 @@ SIGNATURES = {
     "kurbm_gibbs_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
     "kurbm_gibbs_run": (_i, [_vp, _PP, _vp, _sz, _vp, _i, _i, _i, C.c_uint64, C.c_uint64, _i, _i, _i, _i, _vp, _vp, _vp, _i, _sz,
                              _vp, _sz, _vp]),
+    # softmax label units: n_labels follows the parameters; mom is nullable
+    "kurbm_label_sample": (_i, [_vp, _PP, _i, _vp, _i, _i, _RP, _vp, _i, _vp, _i, _vp, _vp]),
+    "kurbm_cd_step_labels": (_i, [_vp, _PP, _i, _vp, _i, _i, _OP, _i, _vp, _sz, _vp, _MP]),
+    "kurbm_cd_epoch_labels": (_i, [_vp, _PP, _i, _vp, _i, _i, _i, _OP, _vp, _sz, _vp, _MP]),
+    "kurbm_class_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "kurbm_class_logits": (_i, [_vp, _PP, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
 }
 
 ABI_VERSION = 5

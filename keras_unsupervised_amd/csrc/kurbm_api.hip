@@ -250,7 +250,7 @@ static Workspace carve(const kurbm_ctx* ctx, void* base, int rows, int n_vis, in
 static int half_step(kurbm_ctx* ctx, int layout, const kurbm_params* p, const float* in, int rows, int ld_in,
                      int act, int noise, const RngArgs* rng, float* out_sample, float* out_prob, float* out_u,
                      int ldo, const float* ref, int ldref, float* colpart, int ld_colpart, int* grid_m_out,
-                     hipStream_t st) {
+                     hipStream_t st, int* cfg_out = nullptr) {
     const int K = (layout == LAYOUT_VH) ? p->n_vis : p->n_hid;
     const int N = (layout == LAYOUT_VH) ? p->n_hid : p->n_vis;
     if (rows <= 0) return fail(KURBM_ERR_ARG, "rows must be positive");
@@ -280,6 +280,7 @@ static int half_step(kurbm_ctx* ctx, int layout, const kurbm_params* p, const fl
     if (rng) g.rng = *rng;
     g.m_fastest = (g.grid_m < g.grid_n) ? 1 : 0;
     if (grid_m_out) *grid_m_out = g.grid_m;
+    if (cfg_out) *cfg_out = cfg;
     HIP_TRY(launch_gemm(layout, cfg, EPI_HALFSTEP, g, st));
     return KURBM_OK;
 }
@@ -518,12 +519,40 @@ size_t kurbm_workspace_bytes(kurbm_ctx* ctx, int rows, int n_vis, int n_hid, int
     return carve(ctx, nullptr, rows, n_vis, n_hid, k).bytes;
 }
 
-// (mom: null = the reference's bare rule on the ordinary kernels; else kurbm_cd_step_mom)
+// ---- softmax label units (include/kurbm.h: kurbm_label_sample) --------------------------
+static int check_labels(const kurbm_params* p, int n_labels) {
+    if (n_labels < 2 || n_labels > 64) return fail(KURBM_ERR_ARG, "n_labels must be in [2, 64], got %d", n_labels);
+    if (n_labels >= p->n_vis) return fail(KURBM_ERR_ARG, "n_labels = %d leaves no pixel among %d visible units", n_labels, p->n_vis);
+    return KURBM_OK;
+}
+
+// The label site behind an h -> v half step (arguments checked by the caller): the block of v is redrawn; with `part` the label
+// columns of that half step's visible-bias partials (row tiles of tile_h rows) are rewritten from ref - v.
+static int label_site(const kurbm_params* p, int n_labels, const float* h, int rows, int ldh, const RngArgs& rng, float* v, int ldv,
+                      float* prob, int ldp, float* out_u, const float* ref, int ldref, float* part, int ld_part, int tile_h,
+                      hipStream_t st) {
+    LabelArgs a;
+    memset(&a, 0, sizeof a);
+    a.h = h; a.ldh = ldh; a.W = p->W; a.ldw = p->ldw; a.b_v = p->b_v;
+    a.v = v; a.ldv = ldv; a.prob = prob; a.ldp = ldp; a.out_u = out_u;
+    a.ref = ref; a.ldref = ldref; a.part = part; a.ld_part = ld_part;
+    a.rows = rows; a.n_pix = p->n_vis - n_labels; a.C = n_labels; a.n_hid = p->n_hid; a.tile_h = tile_h;
+    a.rng = rng;
+    HIP_TRY(launch_label_sample(a, st));
+    return KURBM_OK;
+}
+
+// (mom: null = the reference's bare rule on the ordinary kernels; else kurbm_cd_step_mom.  n_labels: 0 = no label block, exactly
+//  the launches of kurbm_cd_step; else kurbm_cd_step_labels: the label site runs behind every h -> v half step)
 static int cd_step_f32(kurbm_ctx* ctx, const kurbm_params* p, const float* v_batch, int rows, int ldv,
                        const kurbm_cd_opts* o, int which, void* workspace, size_t workspace_bytes, kurbm_stream_t stream,
-                       const kurbm_momentum* mom) {
+                       const kurbm_momentum* mom, int n_labels = 0) {
     if (!ctx || !o) return fail(KURBM_ERR_ARG, "null argument");
     if (int e = check_params(p)) return e;
+    if (n_labels) {
+        if (int e = check_labels(p, n_labels)) return e;
+        if (o->mode != KURBM_MODE_VISIBLE_BERNOULLI) return fail(KURBM_ERR_ARG, "label units need Bernoulli visibles (mode %d)", o->mode);
+    }
     if (rows <= 0) return fail(KURBM_ERR_ARG, "rows must be positive");
     if (bad_matrix(v_batch, ldv, p->n_vis)) return fail(KURBM_ERR_ARG, "v_batch: null, misaligned, ld %% 4 != 0 or ld < n_vis");
     if (o->k < 1 || o->k > 15) return fail(KURBM_ERR_ARG, "k must be in [1, 15]");
@@ -567,9 +596,18 @@ static int cd_step_f32(kurbm_ctx* ctx, const kurbm_params* p, const float* v_bat
         // v_t ~ p(v | h_{t-1})                                    rbm.py:121-123 / :143-144
         r = make_rng(o->seed, o->row0, base + 2u * t - 1u, o->step);
         float* v_out = last ? v_last : w.v_neg;
+        int cfg_v = 0;
         if ((e = half_step(ctx, LAYOUT_HV, p, h_cur, rows, w.ldh, act_v, noise_v, &r, v_out, nullptr, nullptr, ldv,
-                           last ? v_batch : nullptr, ldv, w.part_v, w.ld_part_v, last ? &gm_v : nullptr, st)))
+                           last ? v_batch : nullptr, ldv, w.part_v, w.ld_part_v, last ? &gm_v : nullptr, st, &cfg_v)))
             return e;
+        if (n_labels) {
+            // the label block of v_t is one softmax draw, not C Bernoulli ones: same site, one uniform per row
+            int bm, bn;
+            tile_shape(cfg_v, &bm, &bn);
+            if ((e = label_site(p, n_labels, h_cur, rows, w.ldh, r, v_out, ldv, nullptr, 0, nullptr, last ? v_batch : nullptr, ldv,
+                                last ? w.part_v : nullptr, w.ld_part_v, bm, st)))
+                return e;
+        }
         if (!last) {
             r = make_rng(o->seed, o->row0, base + 2u * t, o->step);
             if ((e = half_step(ctx, LAYOUT_VH, p, v_out, rows, ldv, act_h, NOISE_BERNOULLI, &r, w.h_tmp, nullptr, nullptr,
@@ -749,7 +787,7 @@ int kurbm_cd_epoch_small(kurbm_ctx* ctx, const kurbm_params* p, const float* V, 
 
 static int cd_epoch_f32(kurbm_ctx* ctx, const kurbm_params* p, const float* V, int n_rows, int ldv, int batch_size,
                         const kurbm_cd_opts* opts, void* workspace, size_t workspace_bytes, kurbm_stream_t stream,
-                        const kurbm_momentum* mom) {
+                        const kurbm_momentum* mom, int n_labels = 0) {
     if (!ctx || !opts) return fail(KURBM_ERR_ARG, "null argument");
     if (n_rows < 0 || batch_size <= 0) return fail(KURBM_ERR_ARG, "bad row count / batch size");
     if (opts->delta_out || !opts->apply) return fail(KURBM_ERR_ARG, "kurbm_cd_epoch applies in place: apply = 1, delta_out = null");
@@ -757,7 +795,7 @@ static int cd_epoch_f32(kurbm_ctx* ctx, const kurbm_params* p, const float* V, i
     int steps = 0;
     for (int lo = 0; lo < n_rows; lo += batch_size, ++steps) {
         const int rows = (n_rows - lo < batch_size) ? n_rows - lo : batch_size;
-        if (int e = cd_step_f32(ctx, p, V + (size_t)lo * ldv, rows, ldv, &o, 7, workspace, workspace_bytes, stream, mom)) return e;
+        if (int e = cd_step_f32(ctx, p, V + (size_t)lo * ldv, rows, ldv, &o, 7, workspace, workspace_bytes, stream, mom, n_labels)) return e;
         ++o.step;
     }
     return steps;
@@ -774,6 +812,80 @@ int kurbm_cd_epoch_mom(kurbm_ctx* ctx, const kurbm_params* p, const float* V, in
     if (!opts) return fail(KURBM_ERR_ARG, "null argument");
     if (int e = check_mom(mom, opts)) return e;
     return cd_epoch_f32(ctx, p, V, n_rows, ldv, batch_size, opts, workspace, workspace_bytes, stream, mom);
+}
+
+// ---- softmax label units: the entry points -------------------------------------------------
+int kurbm_label_sample(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* h, int rows, int ldh, const kurbm_rng* rng,
+                       float* v, int ldv, float* prob, int ldp, float* out_u, kurbm_stream_t stream) {
+    if (!ctx || !rng) return fail(KURBM_ERR_ARG, "null argument");
+    if (int e = check_params(p)) return e;
+    if (int e = check_labels(p, n_labels)) return e;
+    if (rows <= 0) return fail(KURBM_ERR_ARG, "rows must be positive");
+    if (bad_matrix(h, ldh, p->n_hid)) return fail(KURBM_ERR_ARG, "h: null, misaligned, ld %% 4 != 0 or ld < n_hid");
+    if (bad_matrix(v, ldv, p->n_vis)) return fail(KURBM_ERR_ARG, "v: null, misaligned, ld %% 4 != 0 or ld < n_vis");
+    if (prob && bad_matrix(prob, ldp, n_labels)) return fail(KURBM_ERR_ARG, "prob: misaligned, ld %% 4 != 0 or ld < n_labels");
+    if (rng->row0 & 3) return fail(KURBM_ERR_ARG, "rng.row0 must be a multiple of 4");
+    const RngArgs r = make_rng(rng->seed, rng->row0, rng->stream_id, rng->step);
+    return label_site(p, n_labels, h, rows, ldh, r, v, ldv, prob, ldp, out_u, nullptr, 0, nullptr, 0, 128,
+                      static_cast<hipStream_t>(stream));
+}
+
+int kurbm_cd_step_labels(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* v_batch, int rows, int ldv,
+                         const kurbm_cd_opts* o, int which, void* workspace, size_t workspace_bytes, kurbm_stream_t stream,
+                         const kurbm_momentum* mom) {
+    if (!ctx || !o) return fail(KURBM_ERR_ARG, "null argument");
+    if (int e = check_params(p)) return e;
+    if (int e = check_labels(p, n_labels)) return e;
+    if (mom)
+        if (int e = check_mom(mom, o)) return e;
+    return cd_step_f32(ctx, p, v_batch, rows, ldv, o, which, workspace, workspace_bytes, stream, mom, n_labels);
+}
+
+int kurbm_cd_epoch_labels(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* V, int n_rows, int ldv, int batch_size,
+                          const kurbm_cd_opts* opts, void* workspace, size_t workspace_bytes, kurbm_stream_t stream,
+                          const kurbm_momentum* mom) {
+    if (!ctx || !opts) return fail(KURBM_ERR_ARG, "null argument");
+    if (int e = check_params(p)) return e;
+    if (int e = check_labels(p, n_labels)) return e;
+    if (mom)
+        if (int e = check_mom(mom, opts)) return e;
+    return cd_epoch_f32(ctx, p, V, n_rows, ldv, batch_size, opts, workspace, workspace_bytes, stream, mom, n_labels);
+}
+
+size_t kurbm_class_workspace_bytes(kurbm_ctx* ctx, int rows, int n_vis, int n_hid) {
+    if (!ctx || rows <= 0 || n_vis <= 0 || n_hid <= 0) return 0;
+    return align_up((size_t)rows * round_up(n_hid, 4) * 4);     // the pre-activation plane a [rows][round_up(n_hid, 4)]
+}
+
+int kurbm_class_logits(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* v, int rows, int ldv, float* logits, int ldl,
+                       float* prob, void* workspace, size_t workspace_bytes, kurbm_stream_t stream) {
+    if (!ctx) return fail(KURBM_ERR_ARG, "ctx is null");
+    if (int e = check_params(p)) return e;
+    if (int e = check_labels(p, n_labels)) return e;
+    if (rows <= 0) return fail(KURBM_ERR_ARG, "rows must be positive");
+    const int n_pix = p->n_vis - n_labels;
+    if (bad_matrix(v, ldv, n_pix)) return fail(KURBM_ERR_ARG, "v: null, misaligned, ld %% 4 != 0 or ld < n_vis - n_labels");
+    if (bad_matrix(logits, ldl, n_labels)) return fail(KURBM_ERR_ARG, "logits: null, misaligned, ld %% 4 != 0 or ld < n_labels");
+    if (prob && !aligned16(prob)) return fail(KURBM_ERR_ARG, "prob is misaligned");
+    if (!workspace || !aligned16(workspace)) return fail(KURBM_ERR_ARG, "workspace is null or misaligned");
+    const size_t need = kurbm_class_workspace_bytes(ctx, rows, p->n_vis, p->n_hid);
+    if (need > workspace_bytes) return fail(KURBM_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // a = v.W[:n_pix] + b_h: the linear half step on a parameter block that ends at the pixel rows (they are W's top rows)
+    kurbm_params pp = *p;
+    pp.n_vis = n_pix;
+    float* a_plane = static_cast<float*>(workspace);
+    const int lda = round_up(p->n_hid, 4);
+    if (int e = half_step(ctx, LAYOUT_VH, &pp, v, rows, ldv, ACT_LINEAR, NOISE_NONE, nullptr, nullptr, a_plane, nullptr, lda, nullptr, 0,
+                          nullptr, 0, nullptr, st))
+        return e;
+    ClassLogitArgs c;
+    memset(&c, 0, sizeof c);
+    c.a = a_plane; c.lda = lda; c.W = p->W; c.ldw = p->ldw; c.b_v = p->b_v;
+    c.logits = logits; c.prob = prob; c.ldl = ldl;
+    c.rows = rows; c.n_pix = n_pix; c.C = n_labels; c.n_hid = p->n_hid;
+    HIP_TRY(launch_class_logits(c, st));
+    return KURBM_OK;
 }
 
 static int apply_delta_f32(kurbm_ctx* ctx, const kurbm_params* p, const float* delta, float lr, int which,

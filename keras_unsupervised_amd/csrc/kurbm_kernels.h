@@ -102,6 +102,35 @@ struct GibbsClampArgs {
 hipError_t launch_gibbs_mask(const unsigned char* clamp, int n_vis, unsigned char* maskp, int npos, int perm, hipStream_t st);
 hipError_t launch_gibbs_clamp(const GibbsClampArgs& a, hipStream_t st);
 
+// kurbm_labels.hip: softmax label units (the last C visible units of a label RBM; include/kurbm.h)
+//   launch_label_sample: the categorical site of the label block behind an h -> v half step.  One workgroup per `tile_h` rows
+//                       (<= 128: the row tile of that half step, so that `part` row blockIdx.x is the tile's row of its column
+//                       partials); v[row][n_pix .. n_pix + C) becomes the one-hot draw from softmax(b_v + h.W^T) with the uniform
+//                       of (row0 + row, col = n_pix) at `rng`; prob [rows][ldp] and out_u [rows] (nullable) receive p and u;
+//                       part (nullable): part[tile][n_pix + c] = sum over the tile's rows of ref - v.
+//   launch_class_logits: logits[row][c] = b_v[n_pix + c] + sum_j softplus(a[row][j] + W[n_pix + c][j]); prob (nullable) their softmax.
+struct LabelArgs {
+    const float* h; int ldh;
+    const float* W; int ldw;       // the WHOLE weight matrix; the label rows start at row n_pix
+    const float* b_v;
+    float* v; int ldv;
+    float* prob; int ldp;
+    float* out_u;
+    const float* ref; int ldref;
+    float* part; int ld_part;
+    int rows, n_pix, C, n_hid, tile_h;
+    RngArgs rng;
+};
+struct ClassLogitArgs {
+    const float* a; int lda;
+    const float* W; int ldw;
+    const float* b_v;
+    float* logits; float* prob; int ldl;
+    int rows, n_pix, C, n_hid;
+};
+hipError_t launch_label_sample(const LabelArgs& a, hipStream_t st);
+hipError_t launch_class_logits(const ClassLogitArgs& a, hipStream_t st);
+
 // Diagnostic hook: the next GEMM launches write their s_memtime stamps here (null = off).
 void set_stamp_buffer(unsigned long long* p);
 void set_debug_off(int mask);

@@ -11,8 +11,11 @@ from .rbm import _unwrap
 
 
 def _dims(layer):
-    """(n_in, n_out) of a layer; n_in is None until the layer is built."""
+    """(n_in, n_out) of a layer; n_in is None until the layer is built.  A label RBM (n_labels > 0) takes the layer below on
+    its PIXEL units: its label block is not fed from below."""
     n_in = layer.input_shape[1] if getattr(layer, "input_shape", None) else None
+    if n_in is not None:
+        n_in -= getattr(layer, "n_labels", 0)
     out_shape = getattr(layer, "output_shape", None)
     n_out = out_shape[1] if out_shape else layer.output_dim
     return n_in, n_out
@@ -26,6 +29,8 @@ class DBN(object):
         (dbn.py:14-32).  An unbuilt layer has no input width yet and is checked when it is built
         by fit / transform."""
         if hasattr(self, "_rbm_layers"):
+            if getattr(self._rbm_layers[-1], "n_labels", 0):
+                raise ValueError("a label RBM is the top of a DBN: nothing stacks on its hidden layer here")
             n_in, _ = _dims(rbm_layer)
             _, prev_out = _dims(self._rbm_layers[-1])
             if n_in is not None and prev_out != n_in:
@@ -48,15 +53,51 @@ class DBN(object):
         layer._ensure_built(X.shape[1])
         return layer._as_device(X)
 
-    def fit(self, V, verbose=1):
+    def _top_labels(self):
+        return getattr(self._layers()[-1], "n_labels", 0)
+
+    def fit(self, V, verbose=1, y=None):
         """Greedy layer-wise training (dbn.py:34-55): fit layer l on V_p, then
-        V_p <- layer.transform(V_p) -- the next layer sees SAMPLED hidden states."""
+        V_p <- layer.transform(V_p) -- the next layer sees SAMPLED hidden states.
+        y (integer labels; needs a label RBM as the top layer): joined to the top layer's input as its one-hot block."""
         layers = self._layers()
+        if (y is not None) != bool(self._top_labels()):
+            raise ValueError("y goes with a label RBM (n_labels > 0) as the top layer, and such a top layer needs y")
+        if len(layers) == 1 and y is not None:
+            print("Train {0:s}.".format(str(layers[0].name)))
+            layers[0].fit(V, verbose=verbose, y=y)
+            return
         V_p, _ = self._to_device(layers[0], V)      # the reference's V.copy(): V itself is never written
         for rbm_layer in layers:
             print("Train {0:s}.".format(str(rbm_layer.name)))                      # dbn.py:53
+            if rbm_layer is layers[-1] and y is not None:
+                rbm_layer.fit(V_p, verbose=verbose, y=y)      # (its features are nobody's input: no transform behind it)
+                break
             rbm_layer.fit(V_p, verbose=verbose)
             V_p = rbm_layer.transform(V_p)
+
+    def predict_proba(self, V):
+        """p(y | v) of a DBN whose top layer is a label RBM, mean-field: the hidden_probs of the lower layers, then the top layer's
+        exact class posterior of those features.  [N, n_labels], where V came from."""
+        return self._classify(V, "predict_proba")
+
+    def predict(self, V):
+        """argmax of predict_proba, integers [N]."""
+        return self._classify(V, "predict")
+
+    def _classify(self, V, what):
+        layers = self._layers()
+        if not self._top_labels():
+            raise ValueError("%s needs a label RBM (n_labels > 0) as the top layer" % what)
+        if len(layers) == 1:
+            return getattr(layers[0], what)(V)
+        V_p, kind = self._to_device(layers[0], V)
+        for rbm_layer in layers[:-1]:
+            V_p = rbm_layer.hidden_probs(V_p)
+        out = getattr(layers[-1], what)(V_p)            # (a DeviceMatrix, or a device tensor of classes)
+        if what == "predict":
+            return out.cpu().numpy() if kind == "numpy" else (out if kind == "device" else out.to(kind))
+        return layers[0]._ret(out, kind, False)
 
     def transform(self, V):
         """Chain of layer.transform (dbn.py:57-75)."""
@@ -84,12 +125,14 @@ class DBN(object):
             V_p = rbm_layer.hidden_probs(V_p)
         return layers[0]._ret(V_p, kind, False)
 
-    def sample(self, n_samples, burn_in=1000, thin=100, n_chains=None, init=None, return_prob=False, seed=None):
+    def sample(self, n_samples, burn_in=1000, thin=100, n_chains=None, init=None, return_prob=False, seed=None, label=None):
         """n_samples "dreams" of the network (extension), [n_samples, n_vis of the first layer]: a Gibbs run in the TOP RBM
         (RBM.sample: burn_in, thin, n_chains, seed as there), then one ancestral pass down through inv_transform of the lower
         layers, in the order of DBN.inv_transform.  init [n_chains, n_vis of the first layer] starts the top chains from its
         sampled representation (layer.transform up to the top RBM's input).  return_prob: the bottom layer's visible_probs of the
-        last hidden states instead of its sample.  A host array, or where init came from."""
+        last hidden states instead of its sample.  A host array, or where init came from.
+        label (a label RBM on top): the class, or one per chain, whose one-hot block the top chains start from and keep; only the
+        pixel part of the top RBM's states goes down."""
         layers = self._layers()
         if not all(layer.built for layer in layers):
             raise ValueError("sample needs built RBM layers")
@@ -99,7 +142,9 @@ class DBN(object):
             for rbm_layer in layers[:-1]:
                 top_init = rbm_layer.transform(top_init)
         n_samples = int(n_samples)
-        H_p, _, _ = layers[-1]._sample(n_samples, n_chains, burn_in, thin, top_init, None, False, seed)
+        H_p, _, _ = layers[-1]._sample(n_samples, n_chains, burn_in, thin, top_init, None, False, seed, label)
+        if self._top_labels() and len(layers) > 1:     # the label block stays up there: the layer below sees the pixel columns
+            H_p = DeviceMatrix(H_p.t, H_p.rows, H_p.cols - self._top_labels(), H_p.ld)
         if H_p.rows != n_samples:                 # (kept, chain) order: the first n_samples rows
             H_p = DeviceMatrix(H_p.t, n_samples, H_p.cols, H_p.ld)
         if len(layers) == 1:

@@ -382,8 +382,10 @@ class DeviceRBM:
 
     def cd_step(self, v, rows, row_start, lr, seed, step, k=1, mode=MODE_VISIBLE_BERNOULLI, chain=0,
                 which=WHICH_ALL, apply=True, emit_delta=False, v_chain=None, row0=0, v_chain_row=0, bf16=False,
-                compute=None, planes=None, momentum=None):
+                compute=None, planes=None, momentum=None, n_labels=0):
         """One CD-k update on rows [row_start, row_start+rows) of DeviceMatrix v.
+
+        n_labels > 0: the last n_labels visible units are a softmax label block (kurbm_cd_step_labels; 'fp32' only).
 
         compute: 'fp32' (fp32 MFMA), 'x3' (fp32 values as exact bf16 triples on the bf16 MFMA),
         'bf16' (operands rounded to bf16).  planes: ResidentPlanes holding these rows (x3: no per-step conversion).
@@ -393,6 +395,23 @@ class DeviceRBM:
         compute = compute or ("bf16" if bf16 else "fp32")
         if momentum is not None and compute == "small":
             raise ValueError("the one-launch 'small' step has no momentum: use 'fp32', 'x3' or 'bf16'")
+        if n_labels:
+            # softmax label units (kurbm_cd_step_labels): the fp32 launches plus the label site behind every h -> v half step
+            if compute != "fp32":
+                raise ValueError("a label RBM trains on the 'fp32' path only, got %r" % (compute,))
+            with torch.cuda.device(self.device):
+                opts = CdOpts(int(k), int(mode), float(lr), 1 if apply else 0,
+                              self.delta_buffer().data_ptr() if emit_delta else None,
+                              v_chain.ptr(v_chain_row) if v_chain is not None else None,
+                              int(seed), int(row0), int(step) & 0xFFFFFFFF, int(chain))
+                ws = self.workspace(rows, k, v.ld)
+                check(self.lib.kurbm_cd_step_labels(self.ctx.handle, C.byref(self.params), int(n_labels), v.ptr(row_start), rows, v.ld,
+                                                    C.byref(opts), int(which), ws.data_ptr(), ws.numel(), self._stream(),
+                                                    C.byref(self._mom(momentum)) if momentum is not None else None))
+            if apply and (which & 1):
+                self._weights_written()
+            self._chain_written(v_chain, mode)
+            return
         # (the plain calls stay as they were, argument for argument: this is the step loop's host path)
         with torch.cuda.device(self.device):
             opts = CdOpts(int(k), int(mode), float(lr), 1 if apply else 0,
@@ -534,11 +553,26 @@ class DeviceRBM:
                 self._weights_written(kept=3)
 
     def cd_epoch(self, v, n_rows, batch_size, lr, seed, step0, k=1, mode=MODE_VISIBLE_BERNOULLI, v_chain=None,
-                 compute="fp32", row_start=0, planes=None, momentum=None):
+                 compute="fp32", row_start=0, planes=None, momentum=None, n_labels=0):
         """All batches of rows [row_start, row_start + n_rows) in ONE library call (fused updates, no score); returns #steps.
-        momentum (see cd_step): one (mu, weight_decay) for the whole call."""
+        momentum (see cd_step): one (mu, weight_decay) for the whole call.  n_labels > 0: kurbm_cd_epoch_labels ('fp32' only)."""
         if momentum is not None and compute == "small":
             raise ValueError("the one-launch 'small' step has no momentum: use 'fp32' or 'x3'")
+        if n_labels:
+            if compute != "fp32":
+                raise ValueError("a label RBM trains on the 'fp32' path only, got %r" % (compute,))
+            with torch.cuda.device(self.device):
+                ws = self.workspace(min(batch_size, max(n_rows, 1)), k, v.ld)
+                opts = CdOpts(int(k), int(mode), float(lr), 1, None, v_chain.ptr() if v_chain is not None else None,
+                              int(seed), 0, int(step0) & 0xFFFFFFFF, 0)
+                n = self.lib.kurbm_cd_epoch_labels(self.ctx.handle, C.byref(self.params), int(n_labels), v.ptr(row_start), int(n_rows),
+                                                   v.ld, int(batch_size), C.byref(opts), ws.data_ptr(), ws.numel(), self._stream(),
+                                                   C.byref(self._mom(momentum)) if momentum is not None else None)
+                if n < 0:
+                    check(n)
+            self._weights_written()
+            self._chain_written(v_chain, mode)
+            return n
         mom = ()
         if momentum is not None:
             with torch.cuda.device(self.device):
@@ -759,6 +793,46 @@ class DeviceRBM:
             if mode == MODE_VISIBLE_BERNOULLI and mask is None:
                 out.bf16_exact = out.binary = True        # 0/1: one bf16 piece, no need to look
         return out, prob
+
+    # -- softmax label units (include/kurbm.h: kurbm_label_sample, kurbm_class_logits) ----------
+    def label_sample(self, h, v, n_labels, seed, stream_id, step, row0=0, want_prob=False, want_u=False):
+        """The label site alone: the last n_labels columns of DeviceMatrix v [rows, n_vis] are REWRITTEN in place as the one-hot
+        draw from softmax(b_v + h.W^T) of the rows of DeviceMatrix h [rows, n_hid]; one uniform per row, u(row0 + row, n_pix) at
+        (stream_id, step).  Returns a dict: prob (DeviceMatrix [rows, n_labels]) and u (device tensor [rows]) as requested."""
+        if h.cols != self.n_hid or v.cols != self.n_vis or h.rows != v.rows:
+            raise ValueError("label_sample: h is (%d, %d), v is (%d, %d); the RBM is %d x %d"
+                             % (h.rows, h.cols, v.rows, v.cols, self.n_vis, self.n_hid))
+        rows = h.rows
+        with torch.cuda.device(self.device):
+            prob = self._alloc_out(rows, int(n_labels), "label_prob") if want_prob else None
+            u = self._alloc_floats(rows, "label_u", zero=False) if want_u else None
+            rng = Rng(int(seed), int(row0), int(stream_id) & 0xFFFFFFFF, int(step) & 0xFFFFFFFF)
+            check(self.lib.kurbm_label_sample(self.ctx.handle, C.byref(self.params), int(n_labels), h.ptr(), rows, h.ld, C.byref(rng),
+                                              v.ptr(), v.ld, prob.ptr() if want_prob else None, prob.ld if want_prob else 0,
+                                              u.data_ptr() if want_u else None, self._stream()))
+        return {"prob": prob, "u": u}
+
+    def class_workspace(self, rows):
+        n = int(self.lib.kurbm_class_workspace_bytes(self.ctx.handle, int(rows), self.n_vis, self.n_hid))
+        if n == 0:
+            raise _lib.KurbmError("kurbm_class_workspace_bytes failed")
+        return self._alloc_bytes(n, "class_workspace", zero=False)
+
+    def class_logits(self, v, n_labels, rows=None, row_start=0, want_prob=True, ws=None):
+        """(logits, prob): DeviceMatrix [rows, n_labels] each (prob None without want_prob) for the pixels of DeviceMatrix v, which
+        has n_vis - n_labels columns or n_vis (the label block is ignored).  Two launches (kurbm_class_logits)."""
+        n_pix = self.n_vis - int(n_labels)
+        if v.cols not in (n_pix, self.n_vis):
+            raise ValueError("input has %d columns, expected %d (pixels) or %d (pixels and labels)" % (v.cols, n_pix, self.n_vis))
+        rows = v.rows - row_start if rows is None else int(rows)
+        with torch.cuda.device(self.device):
+            ws = self.class_workspace(rows) if ws is None else ws
+            logits = self._alloc_out(rows, int(n_labels), "logits")
+            prob = self._alloc_out(rows, int(n_labels), "class_prob") if want_prob else None
+            check(self.lib.kurbm_class_logits(self.ctx.handle, C.byref(self.params), int(n_labels), v.ptr(row_start), rows, v.ld,
+                                              logits.ptr(), logits.ld, prob.ptr() if want_prob else None, ws.data_ptr(), ws.numel(),
+                                              self._stream()))
+        return logits, prob
 
     def score_x3(self, v, rows, row_start, seed, step, mode, chain, planes=None):
         """mean |F(v) - F(v')| of rows [row_start, +rows) of v, v' a fresh one-step reconstruction (rbm.py:225-233), in ONE

@@ -17,7 +17,8 @@ Extensions, all off by default or reference-preserving: ``update_mode='fused'`` 
 feeds all three updates; ``'reference_sequential'`` replays the reference's three chains),
 ``cd_k``, ``persistent`` chains, ``seed``, data-parallel training when torch.distributed is
 initialised, ``verbose=0`` to skip the score passes, ``momentum`` / ``weight_decay`` (both 0 by
-default: the reference's bare rule on the same kernels).
+default: the reference's bare rule on the same kernels), ``n_labels`` (softmax label units: joint training on
+[pixels | one-hot label], ``class_logits`` / ``predict_proba`` / ``predict``, ``sample(label=)``; 0 by default).
 """
 import collections
 import time
@@ -119,6 +120,14 @@ class RBM(object):
         self.compute_dtype = str(opt("compute_dtype", "auto"))
         if self.compute_dtype not in ("fp32", "x3", "bf16", "small", "auto"):
             raise ValueError("compute_dtype must be 'fp32', 'x3', 'bf16', 'small' or 'auto'")
+        # softmax label units (extension): the LAST n_labels visible units are one softmax group -- joint training on
+        # [pixels | one-hot label], exact class posteriors (class_logits / predict_proba / predict), class-conditional samples
+        # (sample(label=)).  include/kurbm.h states the model.  0 = an ordinary RBM, through the same calls as before.
+        self.n_labels = int(opt("n_labels", 0))
+        if self.n_labels != 0 and not 2 <= self.n_labels <= 64:
+            raise ValueError("n_labels must be 0 or in [2, 64], got %d" % self.n_labels)
+        if self.n_labels and mode != MODE_VISIBLE_BERNOULLI:
+            raise ValueError("label units need MODE_VISIBLE_BERNOULLI: the label block is a softmax group among Bernoulli visibles")
         self.list_returns = bool(kwargs.pop("ku_compat_list_returns", True))
         self._device_arg = kwargs.pop("device", None)
         self._init_weights = kwargs.pop("weights", None)
@@ -142,6 +151,8 @@ class RBM(object):
     def build(self, input_shape):
         """Create W ~ U(-0.05, 0.05) [n_vis, n_hid], b_h, b_v on the device (rbm.py:29-40)."""
         n_vis = int(input_shape[1])
+        if self.n_labels and n_vis <= self.n_labels:
+            raise ValueError("%d visible units leave no pixel beside %d label units" % (n_vis, self.n_labels))
         if self._init_weights is not None:
             W, b_h, b_v = self._init_weights
         else:
@@ -261,7 +272,12 @@ class RBM(object):
         if not self.built:
             raise ValueError("inv_transform needs a built RBM (call build / fit / transform first)")
         x, kind = self._as_device(h)
-        return self._ret(self._sample_visible(x), kind, self.list_returns and kind != "device")
+        step = self._call_count
+        out = self._sample_visible(x)
+        if self.n_labels and x.rows > 0:
+            # the label block is one softmax draw (the label site, same stream and call counter), not n_labels Bernoulli ones
+            self._dev.label_sample(x, out, self.n_labels, self.seed, STREAM_INV_TRANSFORM, step)
+        return self._ret(out, kind, self.list_returns and kind != "device")
 
     def call(self, x):
         """The layer's forward pass: stochastic hidden features (rbm.py:80-86)."""
@@ -292,6 +308,8 @@ class RBM(object):
 
     # ------------------------------------------------------------------ likelihood -------
     def _check_likelihood(self, what):
+        if self.n_labels:
+            raise ValueError("%s is not available for a label RBM: the AIS kernels have no softmax site yet" % what)
         if self.mode != MODE_VISIBLE_BERNOULLI:
             raise ValueError("%s is defined for MODE_VISIBLE_BERNOULLI only: in MODE_VISIBLE_GAUSSIAN the hidden site is a "
                              "thresholded relu (rbm.py:58-59), not the Bernoulli unit of an energy model this estimator is valid for"
@@ -376,7 +394,95 @@ class RBM(object):
         v = self._ret(cut(out), kind, False)
         return (v, self._ret(cut(prob), kind, False)) if return_prob else v
 
-    def gibbs(self, v, n_steps=1, clamp=None, return_prob=False, seed=None):
+    # ------------------------------------------------------------------ label units -------
+    def _n_pix(self):
+        return self._dev.n_vis - self.n_labels
+
+    def _labels(self, y, rows):
+        """Integer labels in [0, n_labels) as a host int64 array [rows]; a single integer stands for every row."""
+        y = y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else np.asarray(y)
+        if y.dtype.kind not in "iu":
+            raise ValueError("labels must be integers in [0, %d)" % self.n_labels)
+        y = np.full(rows, int(y), np.int64) if y.ndim == 0 else y.reshape(-1).astype(np.int64)
+        if y.size != rows:
+            raise ValueError("%d labels for %d rows" % (y.size, rows))
+        if y.size and (y.min() < 0 or y.max() >= self.n_labels):
+            raise ValueError("labels must be integers in [0, %d)" % self.n_labels)
+        return y
+
+    def _with_label(self, x, y):
+        """A new DeviceMatrix [rows, n_vis]: the pixel columns of x (n_pix or n_vis wide) and the one-hot block of labels y."""
+        d, n_pix = self._dev, self._n_pix()
+        if x.cols not in (n_pix, d.n_vis):
+            raise ValueError("input has %d columns, expected %d (pixels) or %d (pixels and labels)" % (x.cols, n_pix, d.n_vis))
+        y = self._labels(y, x.rows)
+        with device_guard(d.device):
+            m = DeviceMatrix.zeros(x.rows, d.n_vis, d.device)
+            if x.rows:
+                m.t[:x.rows, :n_pix].copy_(x.t[:x.rows, :n_pix])
+                m.t[torch.arange(x.rows, device=d.device), n_pix + torch.from_numpy(y).to(d.device)] = 1.0
+        return m
+
+    def join(self, V, y):
+        """[pixels | one-hot label]: V [N, n_pix] and integer labels y [N] in [0, n_labels) as one fp32 host array [N, n_pix +
+        n_labels], the layout fit(), transform() and gibbs() of a label RBM take."""
+        if not self.n_labels:
+            raise ValueError("join needs a label RBM (n_labels > 0)")
+        V = _unwrap(V)
+        V = V.detach().cpu().numpy() if isinstance(V, torch.Tensor) else (V.to_numpy() if isinstance(V, DeviceMatrix) else np.asarray(V))
+        if V.ndim != 2:
+            raise ValueError("expected a 2-d array, got shape %s" % (V.shape,))
+        y = self._labels(y, V.shape[0])
+        out = np.zeros((V.shape[0], V.shape[1] + self.n_labels), np.float32)
+        out[:, :V.shape[1]] = V
+        out[np.arange(V.shape[0]), V.shape[1] + y] = 1.0
+        return out
+
+    def _label_clamp(self, clamp, label):
+        """The clamp mask of a Gibbs run on a label RBM: the whole label block (the Gibbs kernels have no softmax site, so a free
+        block would be sampled as independent Bernoulli units) joined with the caller's mask."""
+        d, n_pix = self._dev, self._n_pix()
+        from .engine import clamp_mask
+        m = clamp_mask(clamp, d.n_vis) if clamp is not None else np.zeros(d.n_vis, np.uint8)
+        if label is None and not m[n_pix:].all():
+            raise ValueError("a label RBM samples with its label block clamped: pass label= (or a clamp that covers the whole block "
+                             "and an init that carries it)")
+        m[n_pix:] = 1
+        return m.astype(bool)
+
+    def _class_logits(self, V):
+        self._check_built("class_logits")
+        if not self.n_labels:
+            raise ValueError("class_logits needs a label RBM (n_labels > 0)")
+        x, kind = self._as_device(V)
+        d = self._dev
+        if x.cols not in (self._n_pix(), d.n_vis):
+            raise ValueError("V has %d columns, expected %d (pixels) or %d (pixels and labels)" % (x.cols, self._n_pix(), d.n_vis))
+        if x.rows == 0:
+            e = DeviceMatrix.zeros(0, self.n_labels, d.device)
+            return e, e, kind
+        logits, prob = d.class_logits(x, self.n_labels)
+        return logits, prob, kind
+
+    def class_logits(self, V):
+        """logit_c = b_v[n_pix + c] + sum_j softplus((v.W[:n_pix] + b_h)_j + W[n_pix + c, j]) for the pixels of V, [N, n_labels]:
+        -F(v, y = c) up to the class-independent term v.b_v.  V has n_pix or n_vis columns (a label block is ignored).  Two
+        launches (kurbm_class_logits).  One array, where V came from."""
+        logits, _, kind = self._class_logits(V)
+        return self._ret(logits, kind, False)
+
+    def predict_proba(self, V):
+        """The exact class posterior p(y | v) = softmax(class_logits), [N, n_labels]; rows sum to 1."""
+        _, prob, kind = self._class_logits(V)
+        return self._ret(prob, kind, False)
+
+    def predict(self, V):
+        """argmax_c p(y = c | v) as integers [N] (a host array, or a tensor where V came from)."""
+        logits, _, kind = self._class_logits(V)
+        y = logits.view().argmax(dim=1)
+        return y.cpu().numpy() if kind == "numpy" else (y if kind == "device" else y.to(kind))
+
+    def gibbs(self, v, n_steps=1, clamp=None, return_prob=False, seed=None, label=None):
         """The chains after n_steps Gibbs sweeps from the rows of v (extension; the reference has one half step per call):
         h ~ p(h | v), v ~ p(v | h) at the sites of transform / inv_transform for this mode, in ONE library call
         (kurbm_gibbs_run).  clamp: a boolean mask [n_vis] or a list of unit indices -- those units keep v's values (a
@@ -390,6 +496,14 @@ class RBM(object):
             raise ValueError("n_steps must be >= 1")
         x, kind = self._as_device(v)
         d = self._dev
+        if label is not None and not self.n_labels:
+            raise ValueError("label= needs a label RBM (n_labels > 0)")
+        if self.n_labels:
+            # label RBM: the chains start from the one-hot block of `label` (v: pixels, or pixels and a block that is replaced) and
+            # keep it -- class-conditional sweeps through the same kurbm_gibbs_run
+            clamp = self._label_clamp(clamp, label)
+            if label is not None and x.rows > 0:
+                x = self._with_label(x, label)
         if x.cols != d.n_vis:
             raise ValueError("v has %d columns, the RBM has %d visible units" % (x.cols, d.n_vis))
         if x.rows == 0:
@@ -413,17 +527,19 @@ class RBM(object):
                 m.bf16_exact = m.binary = True
         return m
 
-    def sample(self, n_samples, n_chains=None, burn_in=1000, thin=100, init=None, clamp=None, return_prob=False, seed=None):
+    def sample(self, n_samples, n_chains=None, burn_in=1000, thin=100, init=None, clamp=None, return_prob=False, seed=None, label=None):
         """n_samples draws from the model by Gibbs sampling (extension), [n_samples, n_vis].  n_chains (default n_samples:
         independent chains, one kept sample each) chains run burn_in sweeps; with fewer chains each keeps ceil(n_samples /
         n_chains) states `thin` sweeps apart, and the first n_samples rows in (kept, chain) order are returned.  init: the chains'
         start [n_chains, n_vis]; None starts them at [u < sigmoid(b_v)] (Bernoulli visibles) or b_v (Gaussian).  clamp (mask or
         index list, see gibbs) needs init, which carries the clamped values.  return_prob, seed, the chain bookkeeping and what
-        is left untouched: as gibbs.  The result is a host array, or goes where init came from."""
-        out, prob, kind = self._sample(n_samples, n_chains, burn_in, thin, init, clamp, return_prob, seed)
+        is left untouched: as gibbs.  The result is a host array, or goes where init came from.
+        label (label RBM only): a class, or one class per chain -- the chains start from that one-hot block and keep it
+        (class-conditional samples); init may then hold the pixels alone.  A label RBM refuses to sample with a free block."""
+        out, prob, kind = self._sample(n_samples, n_chains, burn_in, thin, init, clamp, return_prob, seed, label)
         return self._gibbs_out(out, prob, int(n_samples), kind, return_prob)
 
-    def _sample(self, n_samples, n_chains, burn_in, thin, init, clamp, return_prob, seed):
+    def _sample(self, n_samples, n_chains, burn_in, thin, init, clamp, return_prob, seed, label=None):
         """sample() up to the device results: (samples, probs or None -- DeviceMatrix [n_keep * n_chains, n_vis] -- and where
         init came from).  DBN.sample takes the top RBM's states from here without a trip through the host."""
         self._check_built("sample")
@@ -436,16 +552,26 @@ class RBM(object):
             raise ValueError("burn_in and thin must be >= 1")
         if clamp is not None and init is None:
             raise ValueError("clamp needs init: it carries the clamped values")
+        if label is not None and not self.n_labels:
+            raise ValueError("label= needs a label RBM (n_labels > 0)")
         d = self._dev
+        if self.n_labels:
+            clamp = self._label_clamp(clamp, label)
+            if label is not None:
+                label = self._labels(label, n_chains)
         seed = self.seed if seed is None else int(seed)
         kind = "numpy"
         if init is not None:
             x, kind = self._as_device(init)
+            if label is not None and x.rows == n_chains and x.cols == self._n_pix():
+                x = self._with_label(x, label)
             if x.cols != d.n_vis or x.rows != n_chains:
                 raise ValueError("init has shape (%d, %d), expected (%d, %d)" % (x.rows, x.cols, n_chains, d.n_vis))
         chain0 = self._take_chains(n_chains)
         if init is None:
             x = self._start_chains(n_chains, chain0, seed)
+        if label is not None:
+            x = self._with_label(x, label)      # (a copy: the caller's init is never written)
         n_keep = -(-n_samples // n_chains)
         out, prob = d.gibbs_run(x, burn_in=burn_in, thin=thin, n_keep=n_keep, chain0=chain0, seed=seed, mode=self.mode,
                                 clamp=clamp, want_prob=bool(return_prob))
@@ -480,6 +606,16 @@ class RBM(object):
         synchronisation per step."""
         d = self._dev
         base = CHAIN_SCORE * CHAIN_STRIDE
+        if self.n_labels:
+            # label RBM: the reconstruction's label block is drawn by the label site (same site and step as its pixels)
+            act_h, noise_h = hidden_site(self.mode)
+            act_v, noise_v = visible_site(self.mode)
+            fe = d.free_energy(Vd, rows, lo)
+            h = d.half_step("vh", Vd, rows, lo, act_h, noise_h, self.seed, base + 0, step)["sample"]
+            v1 = d.half_step("hv", h, rows, 0, act_v, noise_v, self.seed, base + 1, step)["sample"]
+            d.label_sample(h, v1, self.n_labels, self.seed, base + 1, step)
+            fe_p = d.free_energy(v1, rows, 0)
+            return (fe - fe_p).abs().mean().reshape(1)
         if self._large(rows):
             # one library call on the x3 kernels: same draws (chain CHAIN_SCORE, sites 0 and 1), products on the bf16 pieces
             return d.score_x3(Vd, rows, lo, self.seed, step, self.mode, CHAIN_SCORE, planes=self._planes)
@@ -494,8 +630,31 @@ class RBM(object):
         fe_p = d.free_energy(v1, rows, 0)
         return (fe - fe_p).abs().mean().reshape(1)
 
-    def fit(self, V, verbose=1):
+    def _labelled(self, V, y):
+        """The training matrix of a label RBM as a DeviceMatrix [N, n_vis]: V [N, n_pix] joined with the one-hot block of the
+        integer labels y, or (y None) V [N, n_vis] itself, whose block must be one-hot -- that is checked."""
+        n_cols = V.cols if isinstance(V, DeviceMatrix) else V.shape[1]
+        self._ensure_built(n_cols + (self.n_labels if y is not None else 0))
+        Vd, _ = self._as_device(V)
+        d, n_pix = self._dev, self._n_pix()
+        if y is not None:
+            if Vd.cols != n_pix:
+                raise ValueError("V has %d columns; with y it holds the %d pixels alone" % (Vd.cols, n_pix))
+            return self._with_label(Vd, y)
+        if Vd.cols != d.n_vis:
+            raise ValueError("V has %d columns, the label RBM has %d visible units (%d pixels + %d labels): pass y, or a joined matrix"
+                             % (Vd.cols, d.n_vis, n_pix, self.n_labels))
+        if Vd.rows:
+            blk = Vd.t[:Vd.rows, n_pix:d.n_vis]
+            if not bool((((blk == 0) | (blk == 1)).all() & (blk.sum(dim=1) == 1).all()).item()):
+                raise ValueError("the last %d columns of V must be a one-hot label block (see RBM.join)" % self.n_labels)
+        return Vd
+
+    def fit(self, V, verbose=1, y=None):
         """Train the RBM on V [N, n_vis] by CD-k (rbm.py:100-234).
+
+        y (label RBM only): integer labels in [0, n_labels), joined to V [N, n_pix] as the one-hot label block; without y, V must
+        be n_vis wide and carry that block itself.  A label RBM trains on one GPU.
 
         V: numpy array, torch tensor (host or device) -- uploaded once and kept resident.
         verbose: 1 prints the epoch counter and the per-step score as the reference does
@@ -503,6 +662,12 @@ class RBM(object):
         Returns None.
         """
         V = _unwrap(V)
+        if y is not None and not self.n_labels:
+            raise ValueError("y needs a label RBM (n_labels > 0)")
+        if self.n_labels:
+            if dp.world()[1] > 1:
+                raise ValueError("a label RBM has no data-parallel fit: train it on one GPU")
+            V = self._labelled(V, y)
         n_cols = V.cols if isinstance(V, DeviceMatrix) else V.shape[1]
         self._ensure_built(n_cols)
         Vd, _ = self._as_device(V)
@@ -560,7 +725,7 @@ class RBM(object):
             if whole_epochs:
                 self._update_count += d.cd_epoch(Vd, n, bs, lr, self.seed, self._update_count, k=self.cd_k,
                                                  mode=self.mode, v_chain=self._v_chain if self.persistent else None,
-                                                 compute=self._compute(), planes=planes, **self._mom_kw)
+                                                 compute=self._compute(), planes=planes, **self._mom_kw, **self._label_kw())
                 continue
             if scored_epochs:
                 # small RBMs with the reference's default verbose = 1: the epoch's updates AND scores are queued by one library
@@ -602,6 +767,10 @@ class RBM(object):
         m = self.momentum
         return m[min(int(epoch), len(m) - 1)] if isinstance(m, list) else m
 
+    def _label_kw(self):
+        """The `n_labels=` keyword of the engine's step calls; empty for an ordinary RBM, whose calls stay as they were."""
+        return {"n_labels": self.n_labels} if self.n_labels else {}
+
     def _has_momentum(self):
         m = self.momentum
         return self.weight_decay != 0.0 or (any(x != 0.0 for x in m) if isinstance(m, list) else m != 0.0)
@@ -613,8 +782,12 @@ class RBM(object):
           batch 384 with up to 256, batch 512 with up to 128 -- 21-56 us per step where the multi-launch paths take 55-110;
         * 0/1 data in Bernoulli mode: x3 at every other size (it beats the fp32-MFMA launches from batch 64 on);
         * real-valued data or Gaussian visibles (three pieces per value, seven launches): x3 from rows x n_vis x n_hid >= 6e8 on
-          (batch 1024 at 784 x 1024, 1536 at 784 x 512), the fp32-MFMA kernels below."""
+          (batch 1024 at 784 x 1024, 1536 at 784 x 512), the fp32-MFMA kernels below.
+        The five-launch 'fp32' path whatever was asked once n_labels > 0 -- the same rule as momentum on 'small': the label site
+        exists on that path only (the x3 path for label RBMs is a named follow-up)."""
         c = self.compute_dtype
+        if self.n_labels:
+            return "fp32"
         small_ok = self.cd_k == 1 and not self.persistent and dp.world()[1] == 1 and not self._has_momentum()
         if c == "auto":
             b, h = int(self.hps["batch_size"]), int(self.output_dim)
@@ -632,13 +805,13 @@ class RBM(object):
         if self.update_mode == "fused":
             d.cd_step(Vd, rows, lo, lr, self.seed, step, k=self.cd_k, mode=self.mode, chain=CHAIN_W,
                       v_chain=self._v_chain if self.persistent else None, compute=self._compute(), planes=self._planes,
-                      **self._mom_kw)
+                      **self._mom_kw, **self._label_kw())
         else:
             # the reference's three K.function calls: each its own chain, each seeing the variables
             # the previous call already updated (rbm.py:214-216)
             for chain, which in ((CHAIN_W, _lib.WHICH_W), (CHAIN_BH, _lib.WHICH_BH), (CHAIN_BV, _lib.WHICH_BV)):
                 d.cd_step(Vd, rows, lo, lr, self.seed, step, k=1, mode=self.mode, chain=chain, which=which,
-                          compute=self._compute(), planes=self._planes, **self._mom_kw)
+                          compute=self._compute(), planes=self._planes, **self._mom_kw, **self._label_kw())
 
     def _update_data_parallel(self, Vd, lo, rows, lr, step, rank, world):
         """Each rank: the chain on its rows of the batch -> packed sums -> sum all-reduce (RCCL, inside libkurbm.so) ->
@@ -681,7 +854,7 @@ class RBM(object):
                   "seed": self.seed, "update_mode": self.update_mode, "cd_k": self.cd_k,
                   "persistent": self.persistent, "compute_dtype": self.compute_dtype,
                   "momentum": list(self.momentum) if isinstance(self.momentum, list) else self.momentum,
-                  "weight_decay": self.weight_decay}
+                  "weight_decay": self.weight_decay, "n_labels": self.n_labels}
         return dict(list(self._kwargs.items()) + list(config.items()))
 
 
