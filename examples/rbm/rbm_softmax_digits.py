@@ -14,7 +14,10 @@ softmax head is a torch Linear layer on the same device (it is not part of the h
 
 `rbm_hps` of the JSON config also takes `momentum` (a number, or a list indexed by epoch whose last value holds:
 [0.5, 0.5, 0.5, 0.5, 0.5, 0.9]) and `weight_decay` (on the scale of the batch SUMS that `lr` multiplies); both default to
-0, the reference's bare update rule.
+0, the reference's bare update rule.  `objective` is what `fit` climbs: "generative" (the default: CD, as the reference trains)
+is the only one for this example's plain RBM; "discriminative" and "hybrid" (with `gen_weight`) train a label RBM
+(`n_labels`, `fit(V, y=labels)`) on log p(y | v), which then classifies by itself through `rbm.predict` -- README.md,
+"Discriminative and hybrid training".
 """
 import json
 import os

@@ -630,6 +630,53 @@ size_t kurbm_class_workspace_bytes(kurbm_ctx* ctx, int rows, int n_vis, int n_hi
 int kurbm_class_logits(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* v, int rows, int ldv, float* logits,
                        int ldl, float* prob, void* workspace, size_t workspace_bytes, kurbm_stream_t stream);
 
+/*
+ * Discriminative and hybrid training of a label RBM (Larochelle & Bengio 2008, "Classification using discriminative restricted
+ * Boltzmann machines").  The posterior above is differentiable in closed form; its gradient is exact and needs no Gibbs chain and no
+ * random number.  With n_vis = n_pix + C, U = W[n_pix:] (C x n_hid), d = b_v[n_pix:], a = v_pix.W[:n_pix] + b_h, o_cj = a_j + U_cj,
+ * logit_c = d_c + sum_j softplus(o_cj), p = softmax(logit), t the one-hot block of the row and y the class that is on (the first
+ * unit above 1/2; the callers have checked the block), per row:
+ *     nll    = logsumexp_c(logit) - logit_y            (from the logits, never as -log p_y: finite where p_y has underflowed)
+ *     q_c    = t_c - p_c
+ *     S_y[j] = sigmoid(o_yj)      H_bar[j] = sum_c p_c sigmoid(o_cj)      g_j = S_y[j] - H_bar[j] = sum_c q_c sigmoid(o_cj)
+ * and as batch SUMS, like every update rule of this library, the gradient of sum_rows log p(y | v):
+ *     dW[:n_pix] = v_pix^T.S_y - v_pix^T.H_bar       db_h = sum_rows g
+ *     dU[c][j]   = sum_rows q_c sigmoid(o_cj)        dd_c = sum_rows q_c        db_v[:n_pix] = 0
+ * The update is params += lr * delta through kurbm_apply_delta (kurbm_apply_delta_mom with `mom`).  The hybrid objective
+ * log p(y | v) + gen_weight * log p(v, y) makes ONE update per batch, delta = delta_disc + gen_weight * delta_gen (each product
+ * rounded to fp32, then one fp32 addition), delta_gen being the packed delta kurbm_cd_step_labels emits (apply = 0) on the same
+ * batch at the same weights with the step's own RNG coordinates: both gradients are taken at the same parameters and the velocity
+ * moves once.
+ * Launches of one gradient: the linear v -> h half step on the pixel rows of W and the class-logit launch (those of
+ * kurbm_class_logits), k_class_grad (the plane g, nll, row-tile partials of dU, dd and db_h; S_y and H_bar only for the test hook),
+ * the statistics GEMM of the pixel rows as ONE segment, v_pix^T.g with g = fl(S_y - H_bar) -- half the work of the two-segment
+ * form -- and the reduction of its slabs, and one launch that sums the partials in tile order into the packed delta.  Nothing is
+ * atomic and every sum runs in one fixed order: a call is a deterministic function of its inputs, and a row's S_y, H_bar and nll do
+ * not depend on how many rows share the call.
+ *
+ * kurbm_disc_workspace_bytes: the scratch of all three calls for batches of <= rows (0 for a bad shape).  A hybrid step
+ * (gen_weight > 0) on a batch with ldv > round_up(n_vis, 4) needs the addition kurbm_workspace_bytes states, for the same reason.
+ * kurbm_class_grad (test hook): the planes S_y, H_bar [rows][ldh], nll [rows] (all three nullable) and the packed delta_out
+ *   [dW | db_h | db_v] (required) of v_batch [rows][ldv], whose last n_labels columns are the one-hot block.  Nothing is applied.
+ * kurbm_disc_step: one update.  gen_weight == 0: discriminative; > 0: hybrid, the generative chain running through the label-step
+ *   machinery with opts->k, v_chain, seed, step, row0, chain.  opts->lr is the learning rate; opts->mode must be Bernoulli;
+ *   opts->apply, delta_out and v_planes are not read.  nll_mean (nullable, device float) receives the batch's mean nll BEFORE the update.
+ * kurbm_disc_epoch: contiguous batches of V [n_rows][ldv], remainder last, opts->step advancing by one per batch, no host round
+ *   trip; nll_means (nullable, device [number of batches]) receives each batch's mean.  Returns the number of steps (>= 0).
+ * KURBM_ERR_ARG / KURBM_ERR_WORKSPACE, before anything is enqueued and with nothing written: n_labels outside [2, 64] or >= n_vis,
+ * a negative or non-finite gen_weight, a null or misaligned buffer, ld % 4 != 0 or below the column count, a mode other than
+ * Bernoulli, a bad momentum block, ws_bytes below the query, and (hybrid) whatever kurbm_cd_step_labels refuses.
+ */
+size_t kurbm_disc_workspace_bytes(kurbm_ctx* ctx, int rows, int n_vis, int n_hid, int n_labels);
+int kurbm_class_grad(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* v_batch, int rows, int ldv, float* S_y,
+                     float* H_bar, int ldh, float* nll, float* delta_out, void* ws, size_t ws_bytes, kurbm_stream_t stream);
+int kurbm_disc_step(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* v_batch, int rows, int ldv,
+                    const kurbm_cd_opts* opts, float gen_weight, float* nll_mean /* nullable */, void* ws, size_t ws_bytes,
+                    kurbm_stream_t stream, const kurbm_momentum* mom /* nullable */);
+int kurbm_disc_epoch(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* V, int n_rows, int ldv, int batch_size,
+                     const kurbm_cd_opts* opts, float gen_weight, float* nll_means /* nullable */, void* ws, size_t ws_bytes,
+                     kurbm_stream_t stream, const kurbm_momentum* mom /* nullable */);
+
 #ifdef __cplusplus
 }
 #endif

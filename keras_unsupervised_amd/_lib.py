@@ -130,6 +130,11 @@ SIGNATURES = {
     "kurbm_cd_epoch_labels": (_i, [_vp, _PP, _i, _vp, _i, _i, _i, _OP, _vp, _sz, _vp, _MP]),
     "kurbm_class_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
     "kurbm_class_logits": (_i, [_vp, _PP, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    # discriminative / hybrid training of a label RBM: gen_weight is a float; nll_mean(s) and mom are nullable
+    "kurbm_disc_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
+    "kurbm_class_grad": (_i, [_vp, _PP, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "kurbm_disc_step": (_i, [_vp, _PP, _i, _vp, _i, _i, _OP, C.c_float, _vp, _vp, _sz, _vp, _MP]),
+    "kurbm_disc_epoch": (_i, [_vp, _PP, _i, _vp, _i, _i, _i, _OP, C.c_float, _vp, _vp, _sz, _vp, _MP]),
 }
 
 ABI_VERSION = 5

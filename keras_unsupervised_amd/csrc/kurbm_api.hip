@@ -21,7 +21,7 @@ using namespace kurbm;
 // planner decide".
 enum { KN_LDPAD, KN_X3_F8POS, KN_X3_BYTES, KN_X3_STATS_TALL, KN_BF16_SPLIT, KN_X3_FULL, KN_X3_TALL, KN_X3_MFAST, KN_X3_STATS_MFAST,
        KN_UNFUSED_MIRROR, KN_X3_XCD2D, KN_REDUCE_TR, KN_DP_CHUNKS, KN_X3_STATS_BYTES, KN_MAP_SLOW, KN_X3_PAIR, KN_X3_SPLIT_STATS, KN_X3_ATR, KN_SMALL_LOCAL,
-       KN_COUNT };
+       KN_DISC_STAGE, KN_COUNT };
 constexpr int KN_AUTO = -1;
 static const struct { const char* env; int dflt; } KNOBS[KN_COUNT] = {
     {"KURBM_LDPAD", 0},            // extra elements per bf16 plane row (L2 channel camping probe: no effect)
@@ -49,6 +49,9 @@ static const struct { const char* env; int dflt; } KNOBS[KN_COUNT] = {
                                    //    negative statistics read them through transposed LDS reads (with KURBM_X3_SPLIT_STATS)
     {"KURBM_SMALL_LOCAL", 1},      // 1: the one-launch small step hands h_pos / v_neg between the workgroups of ONE XCD through its L2 (kurbm_small.hip;
                                    //    where the context's probe found the dispatcher dealing consecutive workgroups to consecutive XCDs), 0: every phase over the whole grid
+    {"KURBM_DISC_STAGE", 0},       // measurement (tools/disc_times.py): the launches kurbm_class_grad makes, on the planes a complete call left in its
+                                   //    workspace -- 0: all; 1: the linear half step and k_class_logits; 2: k_class_grad alone; 3: the statistics GEMM,
+                                   //    its slab reduction and k_class_reduce.  kurbm_disc_step / kurbm_disc_epoch do not read it
 };
 
 constexpr size_t STATUS_BYTES = 4096;
@@ -914,6 +917,217 @@ int kurbm_apply_delta_mom(kurbm_ctx* ctx, const kurbm_params* p, const float* de
                           kurbm_stream_t stream, const kurbm_momentum* mom) {
     if (int e = check_mom(mom, nullptr)) return e;
     return apply_delta_f32(ctx, p, delta, lr, which, stream, mom);
+}
+
+// ---- discriminative and hybrid training of a label RBM (include/kurbm.h: kurbm_disc_step) -----------------------------
+// Workspace of a step on `rows` rows: the pre-activation plane, logits and posterior, the gradient plane g, nll, the row-tile
+// partials, the slabs of the pixel-row statistics GEMM, two packed deltas (the step's own and the generative one) and, LAST, the
+// workspace of the generative chain (kurbm_workspace_bytes; a batch wider than round_up(n_vis, 4) grows it as it does there).
+struct DiscWorkspace {
+    float *a, *logits, *prob, *g, *nll, *part, *part_d, *slab, *delta, *gen;
+    void* cd;
+    int ldh, ldl, ld_part, ntiles;
+    size_t slab_stride, cd_bytes, bytes;
+};
+
+// The statistics GEMM of the pixel rows, v_pix^T.g: ONE k segment.  Tiles and grid as plan_outer picks them; the split-K slicing by the
+// same rule on half the k-tiles (k_gemm's walk takes nseg = 1 as it stands: its segment index is t >= nkt, which no tile reaches).
+static OuterPlan plan_outer_one(const kurbm_ctx* ctx, int rows, int m, int n_hid) {
+    OuterPlan pl = plan_outer(ctx, rows, m, n_hid);
+    pl.kt_total = pl.nkt;
+    int s = ctx->force_split > 0 ? ctx->force_split : (2 * ctx->ncu) / (pl.gm * pl.gn);
+    if (s > pl.kt_total) s = pl.kt_total;
+    if (s < 1) s = 1;
+    pl.nsplit_bound = s;
+    pl.kt_per_split = pl.kt_total > 0 ? ceil_div(pl.kt_total, s) : 0;
+    pl.nsplit = pl.kt_total > 0 ? ceil_div(pl.kt_total, pl.kt_per_split) : 1;
+    return pl;
+}
+
+static DiscWorkspace carve_disc(const kurbm_ctx* ctx, void* base, int rows, int n_vis, int n_hid, int C, int ldv_batch = 0) {
+    DiscWorkspace w;
+    const int n_pix = n_vis - C;
+    w.ldh = round_up(n_hid, 4);
+    w.ldl = round_up(C, 4);
+    w.ld_part = w.ldh;
+    w.ntiles = ceil_div(rows, CG_ROWS);
+    const OuterPlan pl = plan_outer_one(ctx, rows, n_pix, n_hid);
+    w.slab_stride = (size_t)n_pix * pl.ld_slab;
+    const size_t packed = (size_t)n_vis * n_hid + n_hid + n_vis;
+    size_t off = 0;
+    char* b = static_cast<char*>(base);
+    auto take = [&](size_t nfloat) { float* q = reinterpret_cast<float*>(b + off); off = align_up(off + nfloat * 4); return q; };
+    w.a = take((size_t)rows * w.ldh);
+    w.logits = take((size_t)rows * w.ldl);
+    w.prob = take((size_t)rows * w.ldl);
+    w.g = take((size_t)rows * w.ldh);
+    w.nll = take((size_t)rows);
+    w.part = take((size_t)w.ntiles * (C + 1) * w.ld_part);
+    w.part_d = take((size_t)w.ntiles * CG_PART_D);
+    w.slab = take(w.slab_stride * pl.nsplit_bound);
+    w.delta = take(packed);
+    w.gen = take(packed);
+    w.cd = b + off;
+    w.cd_bytes = carve(ctx, nullptr, rows, n_vis, n_hid, 1, ldv_batch).bytes;
+    w.bytes = off + w.cd_bytes;
+    return w;
+}
+
+// what every entry point of the family refuses, before anything is enqueued
+static int check_disc(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* v_batch, int rows, int ldv, const void* ws) {
+    if (!ctx) return fail(KURBM_ERR_ARG, "ctx is null");
+    if (int e = check_params(p)) return e;
+    if (int e = check_labels(p, n_labels)) return e;
+    if (rows <= 0) return fail(KURBM_ERR_ARG, "rows must be positive");
+    if (bad_matrix(v_batch, ldv, p->n_vis)) return fail(KURBM_ERR_ARG, "v_batch: null, misaligned, ld %% 4 != 0 or ld < n_vis");
+    if (!ws || !aligned16(ws)) return fail(KURBM_ERR_ARG, "workspace is null or misaligned");
+    return KURBM_OK;
+}
+
+// The launches of one gradient (arguments checked by the caller): the linear half step on the pixel rows of W, k_class_logits,
+// k_class_grad, the statistics GEMM v_pix^T.g (one segment) with the reduction of its slabs into the pixel rows of delta's dW, then
+// k_class_reduce for the rest of the packed delta (+ gen_weight * gen everywhere, when gen is given).  S_y / H_bar (nullable,
+// leading dimension ldh): the caller's planes.
+static int class_grad_launches(kurbm_ctx* ctx, const kurbm_params* p, int C, const float* v_batch, int rows, int ldv,
+                               const DiscWorkspace& w, float* S_y, float* H_bar, int ldh, float* nll, float* delta, const float* gen,
+                               float gen_weight, float* nll_mean, hipStream_t st, int stage = 0) {
+    const int n_pix = p->n_vis - C, n_hid = p->n_hid;
+    kurbm_params pp = *p;
+    pp.n_vis = n_pix;      // (the pixel rows are W's top rows: nothing is copied)
+    // (stage: the measurement knob KURBM_DISC_STAGE -- one group of the launches, on what a complete call left in the workspace)
+    const bool s1 = stage == 0 || stage == 1, s2 = stage == 0 || stage == 2, s3 = stage == 0 || stage == 3;
+    if (s1) {
+        if (int e = half_step(ctx, LAYOUT_VH, &pp, v_batch, rows, ldv, ACT_LINEAR, NOISE_NONE, nullptr, nullptr, w.a, nullptr, w.ldh,
+                              nullptr, 0, nullptr, 0, nullptr, st))
+            return e;
+    }
+    ClassLogitArgs c;
+    memset(&c, 0, sizeof c);
+    c.a = w.a; c.lda = w.ldh; c.W = p->W; c.ldw = p->ldw; c.b_v = p->b_v;
+    c.logits = w.logits; c.prob = w.prob; c.ldl = w.ldl;
+    c.rows = rows; c.n_pix = n_pix; c.C = C; c.n_hid = n_hid;
+    if (s1) HIP_TRY(launch_class_logits(c, st));
+    ClassGradArgs g;
+    memset(&g, 0, sizeof g);
+    g.a = w.a; g.lda = w.ldh; g.W = p->W; g.ldw = p->ldw;
+    g.logits = w.logits; g.prob = w.prob; g.ldl = w.ldl;
+    g.v = v_batch; g.ldv = ldv;
+    g.g = w.g; g.ldg = w.ldh;
+    g.S_y = S_y; g.H_bar = H_bar; g.ldh = ldh;
+    g.nll = nll ? nll : w.nll;
+    g.part = w.part; g.ld_part = w.ld_part; g.part_d = w.part_d;
+    g.rows = rows; g.n_pix = n_pix; g.C = C; g.n_hid = n_hid;
+    if (s2) HIP_TRY(launch_class_grad(g, st));
+    if (!s3) return KURBM_OK;
+    // dW[:n_pix] = v_pix^T.S_y - v_pix^T.H_bar = v_pix^T.g: the statistics GEMM with one segment, M = n_pix
+    const OuterPlan pl = plan_outer_one(ctx, rows, n_pix, n_hid);
+    {
+        GemmArgs m;
+        memset(&m, 0, sizeof m);
+        m.A0 = v_batch; m.lda = ldv;
+        m.B0 = w.g; m.ldb = w.ldh;
+        m.M = n_pix; m.N = n_hid; m.K = rows;
+        m.nseg = 1;
+        m.nkt = pl.nkt; m.kt_total = pl.kt_total; m.kt_per_split = pl.kt_per_split; m.nsplit = pl.nsplit;
+        m.grid_m = pl.gm; m.grid_n = pl.gn;
+        m.slab = w.slab; m.slab_stride = w.slab_stride; m.ld_slab = pl.ld_slab;
+        m.tile_major = ctx->tile_major;
+        HIP_TRY(launch_gemm(LAYOUT_OUTER, pl.cfg, EPI_SLAB, m, st));
+    }
+    ReduceArgs a;
+    memset(&a, 0, sizeof a);
+    a.slab = w.slab; a.slab_stride = w.slab_stride; a.nslab = pl.nsplit; a.ld_slab = pl.ld_slab;
+    a.n_vis = n_pix; a.n_hid = n_hid; a.ldw = 0;
+    a.nblk_w = (int)(((long long)n_pix * (pl.ld_slab / 4) + 255) / 256);
+    if (ctx->tile_major) {
+        tile_shape(pl.cfg, &a.tile_bm, &a.tile_bn);
+        a.grid_m = pl.gm; a.grid_n = pl.gn; a.parts = 4; a.m_fastest = 0;
+        a.nblk_w = pl.gm * pl.gn * a.parts;
+    }
+    a.delta_w = delta;
+    HIP_TRY(launch_reduce_apply(a, st));     // (no bias work: null partial pointers)
+    ClassReduceArgs r;
+    memset(&r, 0, sizeof r);
+    r.part = w.part; r.ld_part = w.ld_part; r.part_d = w.part_d; r.ntiles = w.ntiles;
+    r.nll = g.nll; r.nll_mean = nll_mean; r.rows = rows;
+    r.delta = delta; r.gen = gen; r.gen_weight = gen_weight;
+    r.n_pix = n_pix; r.C = C; r.n_hid = n_hid;
+    HIP_TRY(launch_class_reduce(r, st));
+    return KURBM_OK;
+}
+
+static int disc_step_f32(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* v_batch, int rows, int ldv,
+                         const kurbm_cd_opts* o, float gen_weight, float* nll_mean, void* ws, size_t ws_bytes, kurbm_stream_t stream,
+                         const kurbm_momentum* mom) {
+    if (!o) return fail(KURBM_ERR_ARG, "null argument");
+    if (int e = check_disc(ctx, p, n_labels, v_batch, rows, ldv, ws)) return e;
+    if (!(gen_weight >= 0.f && gen_weight <= 3.4028235e38f)) return fail(KURBM_ERR_ARG, "gen_weight must be finite and >= 0, got %g", (double)gen_weight);
+    if (o->mode != KURBM_MODE_VISIBLE_BERNOULLI) return fail(KURBM_ERR_ARG, "label units need Bernoulli visibles (mode %d)", o->mode);
+    if (nll_mean && (reinterpret_cast<uintptr_t>(nll_mean) & 3u)) return fail(KURBM_ERR_ARG, "nll_mean is misaligned");
+    if (mom)
+        if (int e = check_mom(mom, nullptr)) return e;
+    const bool hybrid = gen_weight > 0.f;
+    const DiscWorkspace w = carve_disc(ctx, ws, rows, p->n_vis, p->n_hid, n_labels, hybrid ? ldv : 0);
+    if (w.bytes > ws_bytes)
+        return fail(KURBM_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu%s", w.bytes, ws_bytes,
+                    hybrid && ldv > round_up(p->n_vis, 4) ? " (ldv > round_up(n_vis, 4): the generative chain keeps v_neg at the batch's leading dimension)" : "");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (hybrid) {
+        // delta_gen: the label step on the same batch at the same weights, emitted and not applied (it checks k, row0, v_chain
+        // before it enqueues anything, and nothing of this step has been enqueued yet)
+        kurbm_cd_opts og = *o;
+        og.apply = 0;
+        og.delta_out = w.gen;
+        og.v_planes = nullptr;
+        if (int e = cd_step_f32(ctx, p, v_batch, rows, ldv, &og, 7, w.cd, w.cd_bytes, stream, nullptr, n_labels)) return e;
+    }
+    if (int e = class_grad_launches(ctx, p, n_labels, v_batch, rows, ldv, w, nullptr, nullptr, 0, nullptr, w.delta,
+                                    hybrid ? w.gen : nullptr, gen_weight, nll_mean, st))
+        return e;
+    return apply_delta_f32(ctx, p, w.delta, o->lr, 7, stream, mom);
+}
+
+size_t kurbm_disc_workspace_bytes(kurbm_ctx* ctx, int rows, int n_vis, int n_hid, int n_labels) {
+    if (!ctx || rows <= 0 || n_vis <= 0 || n_hid <= 0 || n_labels < 2 || n_labels > 64 || n_labels >= n_vis) return 0;
+    return carve_disc(ctx, nullptr, rows, n_vis, n_hid, n_labels).bytes;
+}
+
+int kurbm_class_grad(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* v_batch, int rows, int ldv, float* S_y,
+                     float* H_bar, int ldh, float* nll, float* delta_out, void* ws, size_t ws_bytes, kurbm_stream_t stream) {
+    if (int e = check_disc(ctx, p, n_labels, v_batch, rows, ldv, ws)) return e;
+    if (!delta_out || !aligned16(delta_out)) return fail(KURBM_ERR_ARG, "delta_out is null or misaligned");
+    if ((S_y && bad_matrix(S_y, ldh, p->n_hid)) || (H_bar && bad_matrix(H_bar, ldh, p->n_hid)))
+        return fail(KURBM_ERR_ARG, "S_y / H_bar: misaligned, ld %% 4 != 0 or ld < n_hid");
+    if (nll && (reinterpret_cast<uintptr_t>(nll) & 3u)) return fail(KURBM_ERR_ARG, "nll is misaligned");
+    const DiscWorkspace w = carve_disc(ctx, ws, rows, p->n_vis, p->n_hid, n_labels);
+    if (w.bytes > ws_bytes) return fail(KURBM_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", w.bytes, ws_bytes);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // (S_y and H_bar go straight to the caller's planes, at its leading dimension: nothing else reads them)
+    return class_grad_launches(ctx, p, n_labels, v_batch, rows, ldv, w, S_y, H_bar, ldh, nll, delta_out, nullptr, 0.f, nullptr, st,
+                               ctx->knob[KN_DISC_STAGE]);
+}
+
+int kurbm_disc_step(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* v_batch, int rows, int ldv,
+                    const kurbm_cd_opts* opts, float gen_weight, float* nll_mean, void* ws, size_t ws_bytes, kurbm_stream_t stream,
+                    const kurbm_momentum* mom) {
+    return disc_step_f32(ctx, p, n_labels, v_batch, rows, ldv, opts, gen_weight, nll_mean, ws, ws_bytes, stream, mom);
+}
+
+int kurbm_disc_epoch(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* V, int n_rows, int ldv, int batch_size,
+                     const kurbm_cd_opts* opts, float gen_weight, float* nll_means, void* ws, size_t ws_bytes, kurbm_stream_t stream,
+                     const kurbm_momentum* mom) {
+    if (!ctx || !opts) return fail(KURBM_ERR_ARG, "null argument");
+    if (n_rows < 0 || batch_size <= 0) return fail(KURBM_ERR_ARG, "bad row count / batch size");
+    kurbm_cd_opts o = *opts;
+    int steps = 0;
+    for (int lo = 0; lo < n_rows; lo += batch_size, ++steps) {
+        const int rows = (n_rows - lo < batch_size) ? n_rows - lo : batch_size;
+        if (int e = disc_step_f32(ctx, p, n_labels, V + (size_t)lo * ldv, rows, ldv, &o, gen_weight, nll_means ? nll_means + steps : nullptr,
+                                  ws, ws_bytes, stream, mom))
+            return e;
+        ++o.step;
+    }
+    return steps;
 }
 
 int kurbm_free_energy(kurbm_ctx* ctx, const kurbm_params* p, const float* v, int rows, int ldv, float* F,

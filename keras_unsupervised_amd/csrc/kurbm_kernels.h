@@ -131,6 +131,41 @@ struct ClassLogitArgs {
 hipError_t launch_label_sample(const LabelArgs& a, hipStream_t st);
 hipError_t launch_class_logits(const ClassLogitArgs& a, hipStream_t st);
 
+// kurbm_classgrad.hip: the discriminative gradient of a label RBM (include/kurbm.h, "discriminative and hybrid training")
+//   launch_class_grad:  from a [rows][lda] (the pre-activation plane), logits / prob [rows][ldl] (launch_class_logits) and the one-hot
+//                       block of v [rows][ldv]: the plane g = S_y - H_bar [rows][ldg], S_y and H_bar themselves [rows][ldh] (nullable), nll [rows], and per tile of CG_ROWS rows the partial
+//                       sums part[tile][C + 1][ld_part] (rows c < C: dU[c][.]; row C: db_h) and part_d[tile][CG_PART_D] (dd[c]).
+//   launch_class_reduce: the tiles' partials, in tile order, into rows n_pix .. of dW, db_h and db_v of the packed `delta` (zeros in
+//                       db_v[:n_pix]); with `gen` (a packed generative delta) EVERY element becomes delta + gen_weight * gen -- the
+//                       pixel rows of dW are then read back from `delta`, where the statistics launch in front left them;
+//                       nll_mean (nullable) = the mean of nll[0 .. rows).
+constexpr int CG_ROWS = 32;
+constexpr int CG_THREADS = 256;
+constexpr int CG_PART_D = 64;
+struct ClassGradArgs {
+    const float* a; int lda;
+    const float* W; int ldw;       // the WHOLE weight matrix; the label rows start at row n_pix
+    const float* logits; const float* prob; int ldl;
+    const float* v; int ldv;
+    float* g; int ldg;
+    float* S_y; float* H_bar; int ldh;
+    float* nll;
+    float* part; int ld_part;
+    float* part_d;
+    int rows, n_pix, C, n_hid;
+};
+struct ClassReduceArgs {
+    const float* part; int ld_part;
+    const float* part_d;
+    int ntiles;
+    const float* nll; float* nll_mean; int rows;
+    float* delta;
+    const float* gen; float gen_weight;
+    int n_pix, C, n_hid;
+};
+hipError_t launch_class_grad(const ClassGradArgs& a, hipStream_t st);
+hipError_t launch_class_reduce(const ClassReduceArgs& a, hipStream_t st);
+
 // Diagnostic hook: the next GEMM launches write their s_memtime stamps here (null = off).
 void set_stamp_buffer(unsigned long long* p);
 void set_debug_off(int mask);

@@ -5,7 +5,8 @@ The reference has no EBM-specific format: the example saves the whole Keras mode
 weights.  Both lose part of an RBM: `get_config` omits `mode` (reference ku/ebm/rbm.py:236-242) and
 `visible_bias` is a bare variable outside `get_weights()` (rbm.py:38-40).  Here a checkpoint is
 
-    <stem>.json          get_config() (hps, output_dim, name, mode, seed, update_mode, cd_k, persistent, momentum, weight_decay, n_labels)
+    <stem>.json          get_config() (hps, output_dim, name, mode, seed, update_mode, cd_k, persistent, momentum, weight_decay, n_labels,
+                         objective, gen_weight -- a checkpoint without the last two loads as a generative RBM)
                          + input_dim + the RNG counters, so a reloaded RBM continues the same stream, + the epochs trained
                          (the index into a momentum schedule)
     <stem>.safetensors   rbm_weight [n_vis, n_hid], rbm_hidden_bias [n_hid], rbm_visible_bias [n_vis], fp32;
@@ -33,7 +34,7 @@ def save_rbm(rbm, stem):
     W, b_h, b_v = rbm.get_weights()
     cfg = {k: v for k, v in rbm.get_config().items() if k in
            ("hps", "output_dim", "name", "mode", "seed", "update_mode", "cd_k", "persistent", "compute_dtype", "momentum",
-            "weight_decay", "n_labels")}
+            "weight_decay", "n_labels", "objective", "gen_weight")}
     meta = {"format": "kurbm-rbm", "version": FORMAT_VERSION, "config": cfg, "input_dim": int(W.shape[0]),
             "update_count": int(rbm._update_count), "call_count": int(rbm._call_count),
             "epochs_done": int(getattr(rbm, "_epochs_done", 0))}

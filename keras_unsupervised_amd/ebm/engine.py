@@ -179,6 +179,7 @@ class DeviceRBM:
         # 3 = exact hi/mid/lo split (compute 'x3');  [tensor, stale]
         self._mirrors = {}
         self._ws_b = {}
+        self._ws_disc = None   # (key, rows, buffer): the scratch of disc_step / disc_epoch
         self.velocity = None   # packed [V*H | H | V] fp32 velocity of the momentum steps, allocated (zero) on first use
 
     # -- plumbing -------------------------------------------------------------------
@@ -833,6 +834,83 @@ class DeviceRBM:
                                               logits.ptr(), logits.ld, prob.ptr() if want_prob else None, ws.data_ptr(), ws.numel(),
                                               self._stream()))
         return logits, prob
+
+    # -- discriminative / hybrid training of a label RBM (include/kurbm.h: kurbm_disc_step) ------
+    def disc_workspace(self, rows, n_labels, ldv=0):
+        """Scratch of class_grad / disc_step / disc_epoch for batches of <= rows (kurbm_disc_workspace_bytes).  ldv: the leading
+        dimension of the batch of a HYBRID step when it exceeds round_up(n_vis, 4) (the generative chain keeps v_neg at it)."""
+        n = int(self.lib.kurbm_disc_workspace_bytes(self.ctx.handle, int(rows), self.n_vis, self.n_hid, int(n_labels)))
+        if n == 0:
+            raise _lib.KurbmError("kurbm_disc_workspace_bytes failed")
+        ldc = round_up(self.n_vis, 4)
+        n += round_up(rows * max(int(ldv), ldc) * 4, 256) - round_up(rows * ldc * 4, 256)
+        return self._alloc_bytes(n, "disc_workspace", zero=False)
+
+    def _disc_ws(self, rows, n_labels, ldv):
+        key = (int(n_labels), max(int(ldv), round_up(self.n_vis, 4)))
+        have = self._ws_disc
+        if have is None or have[0] != key or rows > have[1]:
+            have = self._ws_disc = (key, rows, self.disc_workspace(rows, n_labels, ldv))
+        return have[2]
+
+    def class_grad(self, v, n_labels, rows=None, row_start=0, want_planes=True, want_nll=True, ws=None):
+        """The discriminative gradient of rows [row_start, +rows) of DeviceMatrix v [*, n_vis] (label block last) as a dict: S_y and
+        H_bar (DeviceMatrix [rows, n_hid]; None without want_planes), nll (device tensor [rows]; None without want_nll) and delta,
+        the packed [dW | db_h | db_v] sums in this engine's delta buffer.  Nothing is applied (kurbm_class_grad)."""
+        if v.cols != self.n_vis:
+            raise ValueError("input has %d columns, expected %d (pixels and labels)" % (v.cols, self.n_vis))
+        rows = v.rows - row_start if rows is None else int(rows)
+        with torch.cuda.device(self.device):
+            ws = self.disc_workspace(rows, n_labels) if ws is None else ws
+            S_y = self._alloc_out(rows, self.n_hid, "S_y") if want_planes else None
+            H_bar = self._alloc_out(rows, self.n_hid, "H_bar") if want_planes else None
+            nll = self._alloc_floats(rows, "nll", zero=False) if want_nll else None
+            delta = self.delta_buffer()
+            check(self.lib.kurbm_class_grad(self.ctx.handle, C.byref(self.params), int(n_labels), v.ptr(row_start), rows, v.ld,
+                                            S_y.ptr() if want_planes else None, H_bar.ptr() if want_planes else None,
+                                            S_y.ld if want_planes else 0, nll.data_ptr() if want_nll else None, delta.data_ptr(),
+                                            ws.data_ptr(), ws.numel(), self._stream()))
+        return {"S_y": S_y, "H_bar": H_bar, "nll": nll, "delta": delta}
+
+    def disc_step(self, v, rows, row_start, lr, n_labels, gen_weight=0.0, seed=0, step=0, k=1, chain=0, v_chain=None, row0=0,
+                  momentum=None, want_nll=False, ws=None):
+        """One discriminative (gen_weight = 0) or hybrid (gen_weight > 0) update on rows [row_start, +rows) of DeviceMatrix v
+        (kurbm_disc_step).  seed, step, k, chain, v_chain, row0 are those of the generative chain of a hybrid step; momentum as in
+        cd_step.  want_nll: returns a device tensor whose element 0 is the batch's mean nll before the update, else None."""
+        with torch.cuda.device(self.device):
+            opts = CdOpts(int(k), MODE_VISIBLE_BERNOULLI, float(lr), 1, None, v_chain.ptr() if v_chain is not None else None,
+                          int(seed), int(row0), int(step) & 0xFFFFFFFF, int(chain))
+            ws = self._disc_ws(rows, n_labels, v.ld) if ws is None else ws
+            nll = self._alloc_floats(1, "nll_mean", zero=False) if want_nll else None
+            check(self.lib.kurbm_disc_step(self.ctx.handle, C.byref(self.params), int(n_labels), v.ptr(row_start), rows, v.ld,
+                                           C.byref(opts), float(gen_weight), nll.data_ptr() if want_nll else None, ws.data_ptr(),
+                                           ws.numel(), self._stream(), C.byref(self._mom(momentum)) if momentum is not None else None))
+        self._weights_written()
+        if gen_weight > 0:
+            self._chain_written(v_chain, MODE_VISIBLE_BERNOULLI)
+        return nll
+
+    def disc_epoch(self, v, n_rows, batch_size, lr, n_labels, gen_weight=0.0, seed=0, step0=0, k=1, v_chain=None, row_start=0,
+                   momentum=None, want_nll=False, ws=None):
+        """All batches of rows [row_start, +n_rows) in ONE library call (kurbm_disc_epoch); returns #steps, or with want_nll
+        (#steps, device tensor of each batch's mean nll)."""
+        with torch.cuda.device(self.device):
+            opts = CdOpts(int(k), MODE_VISIBLE_BERNOULLI, float(lr), 1, None, v_chain.ptr() if v_chain is not None else None,
+                          int(seed), 0, int(step0) & 0xFFFFFFFF, 0)
+            rows = min(int(batch_size), max(int(n_rows), 1))
+            ws = self._disc_ws(rows, n_labels, v.ld) if ws is None else ws
+            nsteps = (int(n_rows) + int(batch_size) - 1) // int(batch_size)
+            nll = self._alloc_floats(max(nsteps, 1), "nll_means", zero=False) if want_nll else None
+            n = self.lib.kurbm_disc_epoch(self.ctx.handle, C.byref(self.params), int(n_labels), v.ptr(row_start), int(n_rows), v.ld,
+                                          int(batch_size), C.byref(opts), float(gen_weight), nll.data_ptr() if want_nll else None,
+                                          ws.data_ptr(), ws.numel(), self._stream(),
+                                          C.byref(self._mom(momentum)) if momentum is not None else None)
+            if n < 0:
+                check(n)
+        self._weights_written()
+        if gen_weight > 0:
+            self._chain_written(v_chain, MODE_VISIBLE_BERNOULLI)
+        return (n, nll) if want_nll else n
 
     def score_x3(self, v, rows, row_start, seed, step, mode, chain, planes=None):
         """mean |F(v) - F(v')| of rows [row_start, +rows) of v, v' a fresh one-step reconstruction (rbm.py:225-233), in ONE

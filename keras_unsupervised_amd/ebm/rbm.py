@@ -18,7 +18,9 @@ feeds all three updates; ``'reference_sequential'`` replays the reference's thre
 ``cd_k``, ``persistent`` chains, ``seed``, data-parallel training when torch.distributed is
 initialised, ``verbose=0`` to skip the score passes, ``momentum`` / ``weight_decay`` (both 0 by
 default: the reference's bare rule on the same kernels), ``n_labels`` (softmax label units: joint training on
-[pixels | one-hot label], ``class_logits`` / ``predict_proba`` / ``predict``, ``sample(label=)``; 0 by default).
+[pixels | one-hot label], ``class_logits`` / ``predict_proba`` / ``predict``, ``sample(label=)``; 0 by default),
+``objective`` / ``gen_weight`` (what a label RBM's ``fit`` climbs: ``'generative'`` by default, ``'discriminative'`` the exact
+gradient of log p(y | v), ``'hybrid'`` both in one update).
 """
 import collections
 import time
@@ -33,6 +35,7 @@ from .engine import (CHAIN_BH, CHAIN_BV, CHAIN_SCORE, CHAIN_STRIDE, CHAIN_W, MOD
                      DeviceMatrix, DeviceRBM, device_guard, hidden_site, resolve_device, visible_site)
 
 _UPDATE_MODES = ("fused", "reference_sequential")
+_OBJECTIVES = ("generative", "discriminative", "hybrid")
 
 
 def _unwrap(x):
@@ -128,6 +131,18 @@ class RBM(object):
             raise ValueError("n_labels must be 0 or in [2, 64], got %d" % self.n_labels)
         if self.n_labels and mode != MODE_VISIBLE_BERNOULLI:
             raise ValueError("label units need MODE_VISIBLE_BERNOULLI: the label block is a softmax group among Bernoulli visibles")
+        # what fit() of a label RBM climbs (extension; Larochelle & Bengio 2008): 'generative' (default) log p(v, y) by CD, exactly the
+        # calls of before; 'discriminative' the exact gradient of log p(y | v) -- no chain, no random number; 'hybrid'
+        # log p(y | v) + gen_weight log p(v, y), ONE update per batch from both gradients at the same weights.  include/kurbm.h
+        # ("discriminative and hybrid training") states the gradient.  gen_weight is read by 'hybrid' only (the paper's order: 0.01).
+        self.objective = str(opt("objective", "generative"))
+        if self.objective not in _OBJECTIVES:
+            raise ValueError("objective must be one of %s, got %r" % (_OBJECTIVES, self.objective))
+        self.gen_weight = float(opt("gen_weight", 0.01))
+        if self.objective != "generative" and not self.n_labels:
+            raise ValueError("objective %r needs a label RBM (n_labels > 0)" % self.objective)
+        if self.objective == "hybrid" and not (self.gen_weight > 0.0 and np.isfinite(self.gen_weight)):
+            raise ValueError("objective 'hybrid' needs a finite gen_weight > 0, got %r" % self.gen_weight)
         self.list_returns = bool(kwargs.pop("ku_compat_list_returns", True))
         self._device_arg = kwargs.pop("device", None)
         self._init_weights = kwargs.pop("weights", None)
@@ -692,6 +707,8 @@ class RBM(object):
             raise ValueError("the persistent chain has shape (%d, %d); hps['batch_size'] = %d and %d visible units need (%d, %d) -- "
                              "set rbm._v_chain = None to restart the chain from the data"
                              % (self._v_chain.rows, self._v_chain.cols, bs, d.n_vis, bs, d.n_vis))
+        if self.objective != "generative":
+            return self._fit_disc(Vd, n, bs, lr, num_step, verbose)
 
         # x3: the bf16 planes of every window of rows this fit walks are made once, here (the data is the same every
         # epoch); the fallback -- not enough HBM -- is the per-step conversion inside the library
@@ -761,6 +778,50 @@ class RBM(object):
         self._planes = None
         d.check_status()                  # fit() ends with one status read: no later call trains on from a skipped update
         return None
+
+    def _fit_disc(self, Vd, n, bs, lr, num_step, verbose):
+        """The batch loop of fit() for objective 'discriminative' / 'hybrid' (kurbm_disc_step; one GPU, as every label RBM): the
+        epoch call with verbose = 0; with verbose = 1 a step per batch, its score the batch's mean nll = -log p(y | v) BEFORE the
+        update, printed in the reference's format through the score ring.  _update_count advances by one per batch; it is the
+        `step` of the generative chain of a hybrid update, and a discriminative one draws nothing."""
+        d = self._dev
+        if self.update_mode != "fused":
+            raise ValueError("objective %r makes one fused update per batch: update_mode='fused'" % self.objective)
+        gw = self.gen_weight if self.objective == "hybrid" else 0.0
+        kw = dict(gen_weight=gw, seed=self.seed, k=self.cd_k, v_chain=self._v_chain if (self.persistent and gw > 0) else None)
+
+        def print_score(score, label):
+            self.last_scores.append(score)
+            print("\n{0:d}/{1:d}, score: {2:f}".format(label[0], label[1], score))   # rbm.py:234
+        ring = _ScoreRing(d.device, print_score) if verbose == 1 else None
+        for epoch in range(int(self.hps["epochs"])):
+            if verbose == 1:
+                print(epoch + 1, "/", self.hps["epochs"], " epochs", end="\r")
+            mom = {"momentum": (self.momentum_at(self._epochs_done), self.weight_decay)} if self._has_momentum() else {}
+            self._epochs_done += 1
+            if verbose != 1:
+                self._update_count += d.disc_epoch(Vd, n, bs, lr, self.n_labels, step0=self._update_count, **kw, **mom)
+                continue
+            for i in range(num_step):
+                lo, hi = i * bs, min((i + 1) * bs, n)
+                nll = d.disc_step(Vd, hi - lo, lo, lr, self.n_labels, step=self._update_count, want_nll=True, **kw, **mom)
+                self._update_count += 1
+                ring.push(nll, (i + 1, num_step))
+            ring.flush()
+        d.check_status()
+        return None
+
+    def class_log_likelihood(self, V, y):
+        """mean log p(y | v) over the rows of V [N, n_pix] (or [N, n_vis]: the block is ignored) for integer labels y [N], on the
+        host in float64 from class_logits: logit_y - logsumexp(logit), which stays finite where p(y | v) underflows."""
+        logits, _, _ = self._class_logits(V)
+        lg = logits.to_numpy().astype(np.float64)
+        y = self._labels(y, lg.shape[0])
+        if lg.shape[0] == 0:
+            return float("nan")
+        m = lg.max(axis=1)
+        lse = m + np.log(np.exp(lg - m[:, None]).sum(axis=1))
+        return float((lg[np.arange(lg.shape[0]), y] - lse).mean())
 
     def momentum_at(self, epoch):
         """mu of epoch `epoch` (0-based, counted over every fit() of this object): a schedule's last value holds from its end on."""
@@ -854,7 +915,8 @@ class RBM(object):
                   "seed": self.seed, "update_mode": self.update_mode, "cd_k": self.cd_k,
                   "persistent": self.persistent, "compute_dtype": self.compute_dtype,
                   "momentum": list(self.momentum) if isinstance(self.momentum, list) else self.momentum,
-                  "weight_decay": self.weight_decay, "n_labels": self.n_labels}
+                  "weight_decay": self.weight_decay, "n_labels": self.n_labels,
+                  "objective": self.objective, "gen_weight": self.gen_weight}
         return dict(list(self._kwargs.items()) + list(config.items()))
 
 
