@@ -16,6 +16,6 @@ struct kurbm_comm {
 namespace kurbm {
 // In-place sum all-reduce of n floats on stream `st` (any stream of the communicator's device).  0 or KURBM_ERR_*.
 int comm_allreduce_sum(kurbm_comm* c, float* buf, size_t n, hipStream_t st);
-// records the thread-local message kurbm_last_error() returns and passes `code` through (kurbm_api.hip)
+// records the thread-local message kurbm_last_error() returns and passes `code` through (kurbm_host_ctx.hip)
 int fail_msg(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 }  // namespace kurbm

@@ -3,16 +3,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kurbm_plan.h"   // the operand layouts LAYOUT_*, the tile configurations CFG_* and tile_shape()
+
 namespace kurbm {
 
 enum { ACT_SIGMOID = 0, ACT_RELU = 1, ACT_LINEAR = 2 };
 enum { NOISE_NONE = 0, NOISE_BERNOULLI = 1, NOISE_GAUSSIAN = 2 };
 enum { EPI_HALFSTEP = 0, EPI_SLAB = 1, EPI_SOFTPLUS = 2, EPI_AIS = 3 };
-// operand layouts: VH  A=[m][k] B=[k][n];  HV  A=[m][k] B=[n][k];  OUTER  A=[k][m] B=[k][n]
-enum { LAYOUT_VH = 0, LAYOUT_HV = 1, LAYOUT_OUTER = 2 };
-// tile configurations (BM x BN, waves as WAVES_M x WAVES_N); see tile_shape()
-enum { CFG_128x128 = 0, CFG_128x112 = 1, CFG_112x128 = 2, CFG_128x64 = 3, CFG_64x128 = 4, CFG_64x64 = 5,
-       CFG_64x112 = 6, CFG_112x64 = 7, CFG_COUNT = 8 };
 
 struct RngArgs {
     uint32_t seed_lo, seed_hi;
@@ -442,7 +439,6 @@ struct DumpArgs {
 hipError_t launch_dump_plane(const DumpArgs& a, hipStream_t st);
 
 unsigned long long* get_stamp_buffer();
-void tile_shape(int cfg, int* bm, int* bn);
 hipError_t launch_gemm_pb(int epi, const GemmArgsB& g, hipStream_t st);
 // pieces = 1: round to nearest bf16; 3: exact split x = hi + mid + lo, piece j at out + j * out_plane
 // colpart (nullable): [ceil(rows / 64)][ld_colpart] column sums of each 64-row band of `in`
@@ -489,7 +485,7 @@ hipError_t launch_cd1_small(const SmallArgs& a, int nblk, hipStream_t st);
 hipError_t launch_xcc_probe(unsigned* out, int nblk, hipStream_t st);
 hipError_t launch_score_small(const SmallArgs& a, int nblk, hipStream_t st);
 }
-// kurbm_peer.hip <-> kurbm_api.hip
+// kurbm_peer.hip <-> the host layer (kurbm_host_ctx.hip, kurbm_host_dp.hip)
 struct kurbm_ctx;
 struct kurbm_peer;
 namespace kurbm {

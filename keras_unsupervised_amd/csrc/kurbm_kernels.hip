@@ -778,12 +778,6 @@ static hipError_t launch_cfg(const ARGS& g, hipStream_t st) {
     return hipGetLastError();
 }
 
-void tile_shape(int cfg, int* bm, int* bn) {
-    static const int shapes[CFG_COUNT][2] = {{128, 128}, {128, 112}, {112, 128}, {128, 64}, {64, 128}, {64, 64}, {64, 112}, {112, 64}};
-    *bm = shapes[cfg][0];
-    *bn = shapes[cfg][1];
-}
-
 static unsigned long long* g_stamp_buffer = nullptr;
 static int g_dbg_off = 0;
 void set_stamp_buffer(unsigned long long* p) { g_stamp_buffer = p; }

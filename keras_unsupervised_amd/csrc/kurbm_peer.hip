@@ -181,7 +181,7 @@ int launch_sum_band(kurbm_peer* x, unsigned* status, long long band4, long long 
 
 namespace kurbm {
 
-// (kurbm_api.hip: kurbm_cd_step_x3_peer) the exchange of the packed sums that the step has just written to peer_delta(x):
+// (kurbm_host_dp.hip: kurbm_cd_step_x3_peer) the exchange of the packed sums that the step has just written to peer_delta(x):
 // shot 1 here, and what shot 2 -- the reduce / apply launch -- needs to read the bands
 float* peer_delta(kurbm_peer* x) { return delta_of(x->base); }
 int peer_geometry_ok(const kurbm_peer* x, int device, int n_vis, int n_hid) {
