@@ -350,7 +350,16 @@ size_t kurbm_x3_planes_bytes(kurbm_ctx* ctx, int rows, int n_vis, int v_pieces);
 int kurbm_x3_convert_rows(kurbm_ctx* ctx, const float* v, int rows, int ldv, int n_vis, int v_pieces, void* planes,
                           size_t planes_bytes, kurbm_stream_t stream);
 
-/* One half step on the x3 path (transform / test hook): dir 0 = v->h, 1 = h->v. */
+/* One half step on the x3 path (transform / test hook): dir 0 = v->h, 1 = h->v.
+ * in_pieces describes `in` as v_pieces describes a batch: 3 splits any fp32 input into its three pieces; 1 promises that every
+ * element is exactly a bf16 value; 1 | KURBM_V_BINARY promises that every element is 0.0 or 1.0, and the input is then staged as
+ * the k-permuted BYTE plane in which the steps, the Gibbs runs and the score keep their 0/1 data and samples (one byte per
+ * element, any non-zero element read as one) and multiplied by the same kernel instantiation as their half steps -- the only
+ * way to call that kernel on its own.  With KURBM_X3_BYTES = 0 it is staged as one bf16 piece, as it is there.  The workspace is
+ * kurbm_x3_workspace_bytes(rows, ..., in_pieces) for every format; all arguments are checked before anything is enqueued.
+ * Exactness (tests/test_gpu_lattice.py holds every format to it bit for bit): where all operand values are multiples of
+ * power-of-two quanta q_in and q_w, the bias of q_in * q_w, and sum_k |in_k| |w_k| + |bias| <= 2^22 q_in q_w for every output --
+ * and, with in_pieces = 3, the three piece pairs that are left out vanish -- the pre-activation is the exact real-number result. */
 int kurbm_half_step_x3(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t mirror_bytes, int dir,
                        const float* in, int in_pieces, int rows, int ld_in, int act, int noise,
                        const kurbm_rng* rng, float* out_sample, float* out_prob, float* out_u, int ld_out,

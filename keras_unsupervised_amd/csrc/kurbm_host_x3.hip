@@ -158,7 +158,13 @@ static int half_step_any(kurbm_ctx* ctx, int pieces, int in_pieces, const kurbm_
     if (!ctx) return fail_msg(KURBM_ERR_ARG, "ctx is null");
     if (int e = check_params(p)) return e;
     if (dir != 0 && dir != 1) return fail_msg(KURBM_ERR_ARG, "dir must be 0 (v->h) or 1 (h->v)");
-    if (in_pieces != 1 && in_pieces != 3) return fail_msg(KURBM_ERR_ARG, "in_pieces must be 1 or 3");
+    // x3 only: 0/1 input as the byte plane the steps keep their 0/1 data and samples in (step_chain, pf.vbytes); KURBM_X3_BYTES = 0
+    // keeps it one bf16 piece, as it does there
+    const bool in_binary = pieces == 3 && in_pieces == (1 | KURBM_V_BINARY);
+    if (in_binary) in_pieces = 1;
+    if (in_pieces != 1 && in_pieces != 3)
+        return fail_msg(KURBM_ERR_ARG, pieces == 3 ? "in_pieces must be 1, 1 | KURBM_V_BINARY or 3" : "in_pieces must be 1 or 3");
+    const bool in_bytes = in_binary && knob(ctx, KN_X3_BYTES) != 0;
     const int K = dir == 0 ? p->n_vis : p->n_hid, N = dir == 0 ? p->n_hid : p->n_vis;
     if (int e = check_batch(in, rows, ld_in, K, "input")) return e;
     if (noise != NOISE_NONE && (!rng || (rng->row0 & 3))) return fail_msg(KURBM_ERR_ARG, "rng missing or row0 not a multiple of 4");
@@ -175,7 +181,7 @@ static int half_step_any(kurbm_ctx* ctx, int pieces, int in_pieces, const kurbm_
     if (query > need) need = query;
     if (int e = check_mirror_ws(mirror, m.bytes, mirror_bytes, workspace, need, workspace_bytes)) return e;
     uint16_t* Ab = static_cast<uint16_t*>(workspace);
-    HIP_TRY(launch_f32_to_bf16(in, rows, K, ld_in, Ab, Kp, Kb, nullptr, 0, 0, in_pieces, plane, 0, nullptr, 0, st));
+    HIP_TRY(launch_f32_to_bf16(in, rows, K, ld_in, Ab, Kp, Kb, nullptr, 0, 0, in_pieces, plane, 0, nullptr, 0, st, 0, in_bytes ? 1 : 0));
     RngArgs r;
     if (rng) r = make_rng(rng);
     HalfOutB o;
@@ -183,7 +189,7 @@ static int half_step_any(kurbm_ctx* ctx, int pieces, int in_pieces, const kurbm_
     o.prob_f32 = (noise == NOISE_NONE) ? nullptr : out_prob;
     o.out_u = out_u; o.ldo32 = ld_out;
     return half_step_b(ctx, dir == 0 ? LAYOUT_VH : LAYOUT_HV, p, m, Ab, Kp, in_pieces, plane, rows, act, noise,
-                       rng ? &r : nullptr, o, st);
+                       rng ? &r : nullptr, o, st, in_bytes);
 }
 
 // ---- the CD step -----------------------------------------------------------------------

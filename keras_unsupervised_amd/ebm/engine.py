@@ -628,12 +628,20 @@ class DeviceRBM:
         return n, scores
 
     def half_step_bf16(self, direction, x, rows, act, noise, seed, stream_id, step, row0=0, pieces=1, row_start=0,
-                       want_prob=True, want_u=True):
+                       want_prob=True, want_u=True, in_format=None):
         """One half step with bf16 products (pieces=3: the exact split, used by transform() on the x3 path; pieces=1:
-        rounded operands, a test hook); fp32 planes (sample, prob, u) as requested."""
+        rounded operands, a test hook); fp32 planes (sample, prob, u) as requested.
+        in_format (pieces=3 only) forces how the input is staged: 'bytes' (the caller promises 0/1 values: the byte plane of the
+        steps' 0/1 data and samples), 'bf16' (one piece: every value exactly bf16) or 'x3' (three pieces: always legal).
+        None: one piece if x is exactly bf16, else three."""
         n_out = self.n_hid if direction == "vh" else self.n_vis
+        if in_format is not None and (pieces != 3 or in_format not in ("bytes", "bf16", "x3")):
+            raise ValueError("in_format is 'bytes', 'bf16' or 'x3', with pieces=3; got %r with pieces=%d" % (in_format, pieces))
         with torch.cuda.device(self.device):
-            xp = self.v_pieces(x) if pieces == 3 else 1
+            if in_format is not None:
+                xp = {"bytes": 1 | _lib.V_BINARY, "bf16": 1, "x3": 3}[in_format]
+            else:
+                xp = self.v_pieces(x) if pieces == 3 else 1
             mir, ws = self.mirror(pieces), self.workspace_bf16(rows, 1, pieces, xp if pieces == 3 else 1)
             want = {"sample": bool(noise), "prob": bool(want_prob) or not noise, "u": bool(want_u) and bool(noise)}
             out = {k: (self._alloc_out(rows, n_out, k) if want[k] else None) for k in ("sample", "prob", "u")}

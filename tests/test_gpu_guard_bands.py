@@ -297,6 +297,46 @@ def test_half_steps(gpu_device, ctx_option, entry, path, shape, tall):
         assert np.max(np.abs(ob["prob"].to_numpy() - ref())) <= TOL
 
 
+@gpu
+@pytest.mark.parametrize("bytes_knob", [1, 0], ids=["bytes1", "bytes0"])
+@pytest.mark.parametrize("shape", ["S0", "S1", "S2"])
+def test_half_step_x3_byte_plane_input(gpu_device, ctx_option, shape, bytes_knob):
+    """kurbm_half_step_x3 with in_pieces = 1 | KURBM_V_BINARY: the 0/1 input staged as the byte plane of the steps (one bf16 piece
+    with KURBM_X3_BYTES=0), in a workspace of exactly kurbm_x3_workspace_bytes(..., 1 | KURBM_V_BINARY).  Both directions at the
+    Bernoulli sites and the prob-only form: guards intact, guarded == plain, the parity bars of the other formats -- and, the
+    products being the same exact numbers in the same order, bit for bit what the one-piece format gives."""
+    from keras_unsupervised_amd._lib import ACT_SIGMOID, NOISE_BERNOULLI, NOISE_NONE
+    B, nv, nh = SHAPES[shape]
+    ctx_option("KURBM_X3_BYTES", bytes_knob, 1)
+    W, b_h, b_v = synthetic_params(nv, nh, seed=3150 + B)
+    W = (W * np.float32(3.7)).astype(np.float32)
+    v, h = synthetic_binary(B, nv, 3151 + B, p=0.3), synthetic_binary(B, nh, 3152 + B, p=0.5)
+    p = Pair(gpu_device, (W, b_h, b_v))
+    p.B.freeze_params()
+    vA, vB = p.matrix(v, "v")
+    hA, hB = p.matrix(h, "h")
+    rng = O.Rng(SEED, STEP, row0=8)
+
+    def half(e, direction, x, noise, sid, fmt="bytes"):
+        return e.half_step_bf16(direction, x, B, ACT_SIGMOID, noise, SEED, sid, STEP, row0=8, pieces=3, want_u=bool(noise), in_format=fmt)
+
+    for direction, xA, xB, sid, ref in (("vh", vA, vB, 4, lambda: O.sample_hidden(v, W, b_h, rng, 4)),
+                                        ("hv", hA, hB, 5, lambda: O.sample_visible(h, W, b_v, rng, 5))):
+        oa, ob, o1 = half(p.A, direction, xA, NOISE_BERNOULLI, sid), half(p.B, direction, xB, NOISE_BERNOULLI, sid), \
+            half(p.A, direction, xA, NOISE_BERNOULLI, sid, "bf16")
+        p.check()
+        for key in ("sample", "prob", "u"):
+            eq(oa[key].view(), ob[key].view(), "%s bytes: %s" % (direction, key))
+            eq(oa[key].view(), o1[key].view(), "%s bytes against one bf16 piece: %s" % (direction, key))
+        check_half_step(ob, *ref())
+    for direction, xA, xB, ref in (("vh", vA, vB, lambda: O.hidden_prob(v, W, b_h)), ("hv", hA, hB, lambda: O.visible_prob(h, W, b_v))):
+        oa, ob = half(p.A, direction, xA, NOISE_NONE, 0), half(p.B, direction, xB, NOISE_NONE, 0)
+        p.check()
+        assert ob["sample"] is None and ob["u"] is None
+        eq(oa["prob"].view(), ob["prob"].view(), direction + " bytes prob only")
+        assert np.max(np.abs(ob["prob"].to_numpy() - ref())) <= TOL
+
+
 MIRROR = [("kurbm_bf16_mirror_refresh", 1), ("kurbm_x3_mirror_refresh", 3)]
 
 
@@ -903,6 +943,39 @@ def test_full_size_buffers_are_accepted_by_the_same_calls(gpu_device, one_rank_c
     torch.cuda.synchronize()
     r.p.arena.check()
     r.e.check_status()
+
+
+@gpu
+def test_half_step_x3_byte_plane_checks_before_it_enqueues(rig):
+    """in_pieces = 1 | KURBM_V_BINARY: a workspace or a mirror 16 bytes short is refused as for the other formats, an unknown
+    in_pieces is an argument error, nothing in the arena changes either way -- and the same call at full size succeeds."""
+    e, lib = rig.e, rig.e.lib
+
+    def call(in_pieces, short):
+        ws, m3 = rig.buf["wsx"], rig.buf["mir3"]
+        return lib.kurbm_half_step_x3(e.ctx.handle, C.byref(e.params), m3.data_ptr(), m3.numel() - (16 if short == "mir3" else 0), 0,
+                                      rig.V.ptr(), in_pieces, rig.B, rig.V.ld, 0, 1, C.byref(rig.rng), rig.out.ptr(), None, None, rig.out.ld,
+                                      ws.data_ptr(), ws.numel() - (16 if short == "wsx" else 0), e._stream())
+
+    for in_pieces, short, want in ((rig.vp, "wsx", -4), (rig.vp, "mir3", -4), (2, None, -1), (3 | 0x10, None, -1), (0x10, None, -1)):
+        code = call(in_pieces, short)
+        msg = lib.kurbm_last_error()
+        torch.cuda.synchronize()
+        try:
+            rig.p.arena.check()
+        finally:
+            rig.p.arena.freeze_all()
+        assert code == want and msg, (in_pieces, short, code, msg)
+        assert (b"too small" in msg) == (want == -4)
+    for b in rig.p.arena.bufs:
+        b.frozen = None
+    try:
+        assert call(rig.vp, None) == 0, lib.kurbm_last_error()
+        torch.cuda.synchronize()
+        rig.p.arena.check()
+        e.check_status()
+    finally:
+        rig.p.arena.freeze_all()
 
 
 @gpu
