@@ -18,6 +18,12 @@ softmax head is a torch Linear layer on the same device (it is not part of the h
 is the only one for this example's plain RBM; "discriminative" and "hybrid" (with `gen_weight`) train a label RBM
 (`n_labels`, `fit(V, y=labels)`) on log p(y | v), which then classifies by itself through `rbm.predict` -- README.md,
 "Discriminative and hybrid training".
+
+An optional top-level key `"fine_tune"` (absent by default: nothing changes) adds a second classifier after the run: a label RBM
+(`n_labels = 10`) stacked on the trained RBM as a DBN, pretrained greedily on the RBM's mean-field features and then fine-tuned
+end to end on log p(y | v) by `DBN.fine_tune` -- e.g. `{"top_hidden": 128, "top_hps": {"lr": 0.001, "epochs": 5, "batch_size": 128},
+"epochs": 10, "lr": 0.0005, "momentum": 0.5, "weight_decay": 0.0}`.  Its held-out accuracy is printed before and after
+fine-tuning.  README.md, "Fine-tuning a DBN".
 """
 import json
 import os
@@ -31,7 +37,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from ku.ebm import RBM  # noqa: E402
+from ku.ebm import DBN, RBM  # noqa: E402
 from keras_unsupervised_amd.ebm import load_rbm, save_rbm  # noqa: E402
 
 
@@ -134,6 +140,27 @@ class MNISTClassifier(object):
         return acc
 
 
+def fine_tune_demo(mc, ft):
+    """The opt-in "fine_tune" key: a label RBM on top of mc.rbm, greedy pretraining of that top layer, then DBN.fine_tune."""
+    V, y = mc._load_training_data()
+    Vt, yt = mc._load_test_data()
+    top_hps = ft.get("top_hps", mc.conf["rbm_hps"])
+    top = RBM(top_hps, int(ft.get("top_hidden", 128)), name="top", mode=0, n_labels=10, seed=int(ft.get("seed", 11)))
+    dbn = DBN()
+    dbn.add_stack(mc.rbm)
+    dbn.add_stack(top)
+    print("Pretrain the label RBM on the RBM's mean-field features.")
+    top.fit(mc.rbm.hidden_probs(V), y=y, verbose=0)
+    acc = lambda: float((dbn.predict(Vt) == yt).mean()) if yt is not None else float("nan")
+    ll0, acc0 = dbn.class_log_likelihood(V, y), acc()
+    print("Fine-tune every layer on log p(y | v).")
+    dbn.fine_tune(V, y, epochs=ft.get("epochs"), lr=ft.get("lr"), batch_size=ft.get("batch_size"), momentum=ft.get("momentum", 0.0),
+                  weight_decay=ft.get("weight_decay", 0.0), verbose=0)
+    ll1, acc1 = dbn.class_log_likelihood(V, y), acc()
+    print("DBN: mean log p(y | v) on the training set %.4f -> %.4f, held-out accuracy %.4f -> %.4f" % (ll0, ll1, acc0, acc1))
+    return acc0, acc1
+
+
 def main():
     with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "rbm_softmax_conf.json")) as f:
         conf = json.load(f)
@@ -144,6 +171,8 @@ def main():
         mc.test()
     else:
         mc.test()
+    if conf.get("fine_tune"):
+        fine_tune_demo(mc, conf["fine_tune"])
     print("Elapsed time: {0:f}s".format(time.time() - ts))
 
 

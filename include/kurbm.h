@@ -686,6 +686,52 @@ int kurbm_disc_epoch(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const 
                      const kurbm_cd_opts* opts, float gen_weight, float* nll_means /* nullable */, void* ws, size_t ws_bytes,
                      kurbm_stream_t stream, const kurbm_momentum* mom /* nullable */);
 
+/*
+ * Fine-tuning a DBN: backpropagation of sum_rows log p(y | v) through its layers (Hinton & Salakhutdinov 2006; Larochelle & Bengio
+ * 2008, section 6).  The stack is layers l = 1 .. L-1, plain RBMs (W_l [n_{l-1}, n_l], b_h,l), under a top label RBM with
+ * n_pix = n_{L-1}, C classes and (W, b_h, b_v).  Batch SUMS, like every update rule of this library.
+ *   Forward, the mean-field path of DBN.predict_proba:  x_0 = v;  x_l = act_l(x_{l-1}.W_l + b_h,l) -- the prob-only v -> h half step,
+ *     sigmoid (Bernoulli mode) or relu (Gaussian mode), no draw;  the top layer sees [x_{L-1} | one-hot(y)].
+ *   Top layer: g, nll and the packed delta [dW | db_h | db_v] of "discriminative and hybrid training" above, and
+ *     e_{L-1} = g . W[:n_pix]^T                          (rows x n_pix, NO bias term)
+ *   Layer l, going down from L-1, given e_l = dL/dx_l:
+ *     delta_l = e_l * act_l'(x_l)        sigmoid: x_l (1 - x_l);  relu: [x_l > 0];  linear (tests): 1
+ *     dW_l = x_{l-1}^T . delta_l         db_h,l = sum_rows delta_l         db_v,l = 0
+ *     e_{l-1} = delta_l . W_l^T          (no bias; not needed for l = 1)
+ *   Update: every layer's delta is taken at the weights the step started from; the applies come after the last backward launch, each
+ *     layer params += lr * delta through kurbm_apply_delta / kurbm_apply_delta_mom.
+ * Launches of a layer: k_backprop_delta (delta in place over e, row-tile partials of db_h), k_backprop_reduce (the partials in tile
+ * order, in double, rounded once, into db_h; zeros into db_v), the statistics GEMM x_{l-1}^T.delta as ONE segment with the reduction
+ * of its slabs into dW, and, where e_in is wanted, the linear h -> v half step delta.W^T whose bias is the db_v block just zeroed:
+ * the fp32-MFMA launches of the steps above, unchanged.  No allocation, no host synchronisation, no random number, nothing atomic,
+ * every sum in one fixed order: a call is a deterministic function of its inputs, and a row's delta and e_in do not depend on how
+ * many rows share the call.
+ *
+ * kurbm_backprop_workspace_bytes: the scratch of kurbm_backprop_layer on a layer of n_in x n_out units for batches of <= rows (0 for
+ *   a bad shape).  kurbm_backprop_delta takes the query at n_in = 1.
+ * kurbm_backprop_delta (test hook): the site alone.  e, x_out [rows][n_hid]; delta [rows][ldd] (it may equal e, with ldd == lde);
+ *   db_h [n_hid].  Columns [n_hid, ld) of every plane are neither read into a result nor written.
+ * kurbm_backprop_layer: p = the layer's parameters (b_h and b_v are not read, but the block is checked as everywhere), x_in [rows][ldin] its input (n_vis columns), x_out [rows][ldout]
+ *   its output as the forward pass left it, e [rows][lde] dL/dx_out on entry and delta on return, delta_out the packed
+ *   [dW | db_h | db_v = 0] (required), e_in (nullable) [rows][ldei] dL/dx_in.  delta_out does not depend on whether e_in is given.
+ * kurbm_disc_backprop: the launches of kurbm_class_grad on v_batch [rows][ldv] (label block last), then e_in (nullable)
+ *   [rows][ldei] = g.W[:n_pix]^T.  Nothing is applied.  delta_out and nll_mean (nullable, device float: the batch's mean nll) are bit
+ *   for bit those of kurbm_class_grad / kurbm_disc_step on the same batch.  Workspace: kurbm_disc_workspace_bytes, nothing more (the
+ *   product reads the plane g there, and its zero bias is db_v[:n_pix] of delta_out).
+ * KURBM_ERR_ARG / KURBM_ERR_WORKSPACE, before anything is enqueued and with nothing written: a null or misaligned buffer, ld % 4 != 0
+ * or below the column count, an act that is none of KURBM_ACT_*, rows <= 0, ws_bytes below the query, and for kurbm_disc_backprop
+ * whatever kurbm_class_grad refuses.
+ */
+size_t kurbm_backprop_workspace_bytes(kurbm_ctx* ctx, int rows, int n_in, int n_out);
+int kurbm_backprop_delta(kurbm_ctx* ctx, const float* e, int lde, const float* x_out, int ldx, int rows, int n_hid, int act,
+                         float* delta, int ldd, float* db_h, void* ws, size_t ws_bytes, kurbm_stream_t stream);
+int kurbm_backprop_layer(kurbm_ctx* ctx, const kurbm_params* p, int act, const float* x_in, int ldin, const float* x_out, int ldout,
+                         float* e, int lde, int rows, float* delta_out, float* e_in /* nullable */, int ldei, void* ws,
+                         size_t ws_bytes, kurbm_stream_t stream);
+int kurbm_disc_backprop(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* v_batch, int rows, int ldv,
+                        float* delta_out, float* e_in /* nullable */, int ldei, float* nll_mean /* nullable */, void* ws,
+                        size_t ws_bytes, kurbm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,11 @@ SIGNATURES = {
     "kurbm_class_grad": (_i, [_vp, _PP, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "kurbm_disc_step": (_i, [_vp, _PP, _i, _vp, _i, _i, _OP, C.c_float, _vp, _vp, _sz, _vp, _MP]),
     "kurbm_disc_epoch": (_i, [_vp, _PP, _i, _vp, _i, _i, _i, _OP, C.c_float, _vp, _vp, _sz, _vp, _MP]),
+    # fine-tuning a DBN: the backward pass of a layer and of the top label RBM; e_in and nll_mean are nullable
+    "kurbm_backprop_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "kurbm_backprop_delta": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    "kurbm_backprop_layer": (_i, [_vp, _PP, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _sz, _vp]),
+    "kurbm_disc_backprop": (_i, [_vp, _PP, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
 }
 
 ABI_VERSION = 5

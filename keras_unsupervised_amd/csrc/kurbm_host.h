@@ -14,6 +14,7 @@
 #include "kurbm_plan.h"
 
 static_assert(kurbm::DISC_TILE_ROWS == kurbm::CG_ROWS && kurbm::DISC_PART_D == kurbm::CG_PART_D, "kurbm_plan.h and kurbm_kernels.h disagree");
+static_assert(kurbm::BACKPROP_TILE_ROWS == kurbm::BP_ROWS, "kurbm_plan.h and kurbm_kernels.h disagree");
 
 constexpr size_t STATUS_BYTES = 4096;
 struct kurbm_ctx {

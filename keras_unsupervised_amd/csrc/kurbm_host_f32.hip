@@ -531,6 +531,43 @@ static int disc_step_f32(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, co
     return apply_delta_f32(ctx, p, w.delta, o->lr, 7, stream, mom);
 }
 
+// ---- fine-tuning a DBN (include/kurbm.h: kurbm_backprop_layer) ---------------------------------------------------------------
+// the operands of the activation-derivative site: e and x_out [rows][n_hid], delta [rows][n_hid] (it may BE e, at e's leading dimension)
+static int check_site(const float* e, int lde, const float* x_out, int ldx, int rows, int n_hid, int act, const float* delta, int ldd) {
+    if (int err = check_batch(e, rows, lde, n_hid, "e")) return err;
+    if (int err = check_batch(x_out, rows, ldx, n_hid, "x_out")) return err;
+    if (act < ACT_SIGMOID || act > ACT_LINEAR) return fail_msg(KURBM_ERR_ARG, "unknown activation %d", act);
+    if (bad_matrix(delta, ldd, n_hid)) return fail_msg(KURBM_ERR_ARG, "delta: null, misaligned, ld %% 4 != 0 or ld < n_hid");
+    if (delta == e && ldd != lde) return fail_msg(KURBM_ERR_ARG, "delta in place over e needs ldd == lde");
+    return KURBM_OK;
+}
+// k_backprop_delta and k_backprop_reduce (arguments checked by the caller): delta, db_h [n_hid] and, where given, n_vis zeros at db_v
+static int site_launches(const float* e, int lde, const float* x_out, int ldx, int rows, int n_hid, int act, float* delta, int ldd,
+                         const BackpropWorkspace& w, float* db_h, float* db_v, int n_vis, hipStream_t st) {
+    BackpropDeltaArgs d;
+    memset(&d, 0, sizeof d);
+    d.e = e; d.lde = lde; d.x = x_out; d.ldx = ldx; d.delta = delta; d.ldd = ldd;
+    d.part = w.part; d.ld_part = w.ld_part;
+    d.rows = rows; d.n_hid = n_hid; d.act = act;
+    HIP_TRY(launch_backprop_delta(d, st));
+    BackpropReduceArgs r;
+    memset(&r, 0, sizeof r);
+    r.part = w.part; r.ld_part = w.ld_part; r.ntiles = w.ntiles; r.n_hid = n_hid; r.n_vis = n_vis;
+    r.db_h = db_h; r.db_v = db_v;
+    HIP_TRY(launch_backprop_reduce(r, st));
+    return KURBM_OK;
+}
+// e_in = delta.W[:n_in]^T: the linear h -> v half step on the first n_in rows of W (they are its top rows: nothing is copied), with
+// `zero_bias`, n_in zeros on the device, in the bias's place -- x + 0.0f is x, so the launch and its bits are those of every other
+// linear h -> v half step
+static int backprop_input(kurbm_ctx* ctx, const kurbm_params* p, int n_in, const float* delta, int rows, int ldd, const float* zero_bias,
+                          float* e_in, int ldei, hipStream_t st) {
+    kurbm_params pp = *p;
+    pp.n_vis = n_in;
+    pp.b_v = const_cast<float*>(zero_bias);
+    return half_step_plain(ctx, LAYOUT_HV, &pp, delta, rows, ldd, ACT_LINEAR, NOISE_NONE, nullptr, e_in, ldei, st);
+}
+
 // ---- annealed importance sampling (include/kurbm.h: kurbm_ais_run) ---------------------
 // One temperature: v -> h launch (h and the softplus-difference partials), the accumulate step (it reads the (b_v - b_A).v
 // partials the PREVIOUS temperature -- or the start -- left in vpart, so it runs before they are rewritten), h -> v launch
@@ -624,6 +661,65 @@ int kurbm_disc_epoch(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const 
         ++o.step;
         return e;
     });
+}
+
+// ---- fine-tuning a DBN: backpropagation of log p(y | v) through its layers (include/kurbm.h: kurbm_backprop_layer) ------------
+size_t kurbm_backprop_workspace_bytes(kurbm_ctx* ctx, int rows, int n_in, int n_out) {
+    if (!ctx || rows <= 0 || n_in <= 0 || n_out <= 0) return 0;
+    return carve_backprop(&ctx->plan, nullptr, rows, n_in, n_out).bytes;
+}
+
+int kurbm_backprop_delta(kurbm_ctx* ctx, const float* e, int lde, const float* x_out, int ldx, int rows, int n_hid, int act,
+                         float* delta, int ldd, float* db_h, void* ws, size_t ws_bytes, kurbm_stream_t stream) {
+    if (!ctx) return fail_msg(KURBM_ERR_ARG, "ctx is null");
+    if (n_hid <= 0) return fail_msg(KURBM_ERR_ARG, "n_hid must be positive");
+    if (int err = check_site(e, lde, x_out, ldx, rows, n_hid, act, delta, ldd)) return err;
+    if (!db_h || (reinterpret_cast<uintptr_t>(db_h) & 3u)) return fail_msg(KURBM_ERR_ARG, "db_h is null or misaligned");
+    const BackpropWorkspace w = carve_backprop(&ctx->plan, ws, rows, 1, n_hid);
+    if (int err = check_workspace(ws, w.bytes, ws_bytes)) return err;
+    return site_launches(e, lde, x_out, ldx, rows, n_hid, act, delta, ldd, w, db_h, nullptr, 0, static_cast<hipStream_t>(stream));
+}
+
+int kurbm_backprop_layer(kurbm_ctx* ctx, const kurbm_params* p, int act, const float* x_in, int ldin, const float* x_out, int ldout,
+                         float* e, int lde, int rows, float* delta_out, float* e_in, int ldei, void* ws, size_t ws_bytes,
+                         kurbm_stream_t stream) {
+    if (!ctx) return fail_msg(KURBM_ERR_ARG, "ctx is null");
+    if (int err = check_params(p)) return err;
+    if (int err = check_batch(x_in, rows, ldin, p->n_vis, "x_in")) return err;
+    if (int err = check_site(e, lde, x_out, ldout, rows, p->n_hid, act, e, lde)) return err;
+    if (!delta_out || !aligned16(delta_out)) return fail_msg(KURBM_ERR_ARG, "delta_out is null or misaligned");
+    if (e_in && bad_matrix(e_in, ldei, p->n_vis)) return fail_msg(KURBM_ERR_ARG, "e_in: misaligned, ld %% 4 != 0 or ld < n_vis");
+    const BackpropWorkspace w = carve_backprop(&ctx->plan, ws, rows, p->n_vis, p->n_hid);
+    if (int err = check_workspace(ws, w.bytes, ws_bytes)) return err;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int n_vis = p->n_vis, n_hid = p->n_hid;
+    const size_t nw = (size_t)n_vis * n_hid;
+    // delta = e * act'(x_out) in place, db_h, and the zeros of db_v
+    if (int err = site_launches(e, lde, x_out, ldout, rows, n_hid, act, e, lde, w, delta_out + nw, delta_out + nw + n_hid, n_vis, st)) return err;
+    // dW = x_in^T.delta: the statistics GEMM with one segment, as class_grad_launches runs it
+    const OuterPlan pl = plan_outer_one(&ctx->plan, rows, n_vis, n_hid);
+    if (int err = outer_slabs(ctx, x_in, e, nullptr, nullptr, rows, n_vis, n_hid, ldin, lde, w.slab, w.slab_stride, pl, st)) return err;
+    ReduceArgs a = stats_reduce_args(ctx, pl, w.slab, w.slab_stride, n_vis, n_hid, 0);
+    a.delta_w = delta_out;
+    HIP_TRY(launch_reduce_apply(a, st));     // (no bias work: null partial pointers)
+    if (!e_in) return KURBM_OK;
+    return backprop_input(ctx, p, n_vis, e, rows, lde, delta_out + nw + n_hid, e_in, ldei, st);
+}
+
+int kurbm_disc_backprop(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* v_batch, int rows, int ldv, float* delta_out,
+                        float* e_in, int ldei, float* nll_mean, void* ws, size_t ws_bytes, kurbm_stream_t stream) {
+    if (int err = check_disc(ctx, p, n_labels, v_batch, rows, ldv, ws)) return err;
+    if (!delta_out || !aligned16(delta_out)) return fail_msg(KURBM_ERR_ARG, "delta_out is null or misaligned");
+    if (e_in && bad_matrix(e_in, ldei, p->n_vis - n_labels)) return fail_msg(KURBM_ERR_ARG, "e_in: misaligned, ld %% 4 != 0 or ld < n_pix");
+    if (nll_mean && (reinterpret_cast<uintptr_t>(nll_mean) & 3u)) return fail_msg(KURBM_ERR_ARG, "nll_mean is misaligned");
+    const DiscWorkspace w = carve_disc(&ctx->plan, ws, rows, p->n_vis, p->n_hid, n_labels);
+    if (int err = check_workspace(ws, w.bytes, ws_bytes)) return err;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int err = class_grad_launches(ctx, p, n_labels, v_batch, rows, ldv, w, nullptr, nullptr, 0, nullptr, delta_out, nullptr, 0.f, nll_mean, st))
+        return err;
+    if (!e_in) return KURBM_OK;
+    // e = g.W[:n_pix]^T on the plane g the gradient left in the workspace; the zero bias: db_v[:n_pix] of the delta just written
+    return backprop_input(ctx, p, p->n_vis - n_labels, w.g, rows, w.ldh, delta_out + (size_t)p->n_vis * p->n_hid + p->n_hid, e_in, ldei, st);
 }
 
 int kurbm_apply_delta(kurbm_ctx* ctx, const kurbm_params* p, const float* delta, float lr, int which,

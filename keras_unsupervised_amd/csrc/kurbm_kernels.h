@@ -163,6 +163,30 @@ struct ClassReduceArgs {
 hipError_t launch_class_grad(const ClassGradArgs& a, hipStream_t st);
 hipError_t launch_class_reduce(const ClassReduceArgs& a, hipStream_t st);
 
+// kurbm_backprop.hip: the activation-derivative site of a layer's backward pass (include/kurbm.h, "fine-tuning a DBN")
+//   launch_backprop_delta:  delta[r][j] = e[r][j] * act'(x[r][j]) for j < n_hid (delta may be e: in place), and per tile of BP_ROWS rows
+//                           the column sums part[tile][j] of delta, rows in order.  Columns [n_hid, ld) are neither read into a
+//                           result nor written.
+//   launch_backprop_reduce: db_h[j] = the tiles' partials summed in tile order (double, rounded once); db_v[0 .. n_vis) = 0 (nullable).
+constexpr int BP_ROWS = 16;       // rows per tile
+constexpr int BP_THREADS = 64;    // one wave, four columns per thread: a slice of BP_COLS columns
+constexpr int BP_COLS = 4 * BP_THREADS;
+struct BackpropDeltaArgs {
+    const float* e; int lde;
+    const float* x; int ldx;
+    float* delta; int ldd;
+    float* part; int ld_part;
+    int rows, n_hid, act;
+};
+struct BackpropReduceArgs {
+    const float* part; int ld_part;
+    int ntiles, n_hid, n_vis;
+    float* db_h;
+    float* db_v;
+};
+hipError_t launch_backprop_delta(const BackpropDeltaArgs& a, hipStream_t st);
+hipError_t launch_backprop_reduce(const BackpropReduceArgs& a, hipStream_t st);
+
 // Diagnostic hook: the next GEMM launches write their s_memtime stamps here (null = off).
 void set_stamp_buffer(unsigned long long* p);
 void set_debug_off(int mask);

@@ -365,6 +365,28 @@ inline DiscWorkspace carve_disc(const PlanCtx* ctx, void* base, int rows, int n_
     return w;
 }
 
+// A layer's backward pass on `rows` rows (kurbm_backprop_layer; n_in x n_out = the layer's n_vis x n_hid): the row-tile partials of
+// db_h (tiles of BACKPROP_TILE_ROWS rows: kurbm_backprop.hip) FIRST -- kurbm_backprop_delta, the site alone, uses nothing else and
+// takes the query at n_in = 1 -- then the slabs of the statistics GEMM x_in^T.delta.
+constexpr int BACKPROP_TILE_ROWS = 16;   // = BP_ROWS of kurbm_kernels.h (asserted where both are seen)
+struct BackpropWorkspace {
+    float *part, *slab;
+    int ld_part, ntiles;
+    size_t slab_stride, bytes;
+};
+inline BackpropWorkspace carve_backprop(const PlanCtx* ctx, void* base, int rows, int n_in, int n_out) {
+    BackpropWorkspace w;
+    w.ld_part = round_up(n_out, 4);
+    w.ntiles = ceil_div(rows, BACKPROP_TILE_ROWS);
+    const OuterPlan pl = plan_outer_one(ctx, rows, n_in, n_out);
+    w.slab_stride = (size_t)n_in * pl.ld_slab;
+    Arena ar(base);
+    w.part = ar.take<float>((size_t)w.ntiles * w.ld_part);
+    w.slab = ar.take<float>(w.slab_stride * pl.nsplit_bound);
+    w.bytes = ar.off;
+    return w;
+}
+
 // The weight mirror of the bf16 / x3 paths: `pieces` bf16 planes of W and of W^T, k-padded to 128
 struct Mirror { uint16_t *Wb, *Wtb; int Kh, Kv, ldW, ldWt, pieces; size_t planeW, planeWt, bytes; };
 inline Mirror carve_mirror(const PlanCtx* ctx, void* base, int n_vis, int n_hid, int pieces) {

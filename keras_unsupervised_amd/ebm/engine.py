@@ -180,6 +180,7 @@ class DeviceRBM:
         self._mirrors = {}
         self._ws_b = {}
         self._ws_disc = None   # (key, rows, buffer): the scratch of disc_step / disc_epoch
+        self._ws_bp = None     # (rows, buffer): the scratch of backprop_layer
         self.velocity = None   # packed [V*H | H | V] fp32 velocity of the momentum steps, allocated (zero) on first use
 
     # -- plumbing -------------------------------------------------------------------
@@ -919,6 +920,76 @@ class DeviceRBM:
         if gen_weight > 0:
             self._chain_written(v_chain, MODE_VISIBLE_BERNOULLI)
         return (n, nll) if want_nll else n
+
+    # -- fine-tuning a DBN (include/kurbm.h: kurbm_backprop_layer) -------------------------------
+    def probs_into(self, x, rows, row_start, act, out, out_row=0):
+        """The prob-only v -> h half step of rows [row_start, +rows) of DeviceMatrix x, written into rows [out_row, +rows) of the
+        caller's plane `out` at ITS leading dimension (out.cols >= n_hid: the first n_hid columns are written, the rest is left
+        alone) -- a lower layer's activations go straight into the pixel columns of the top layer's batch plane.  fp32 MFMA, no draw."""
+        if x.cols != self.n_vis or out.cols < self.n_hid:
+            raise ValueError("input has %d columns and the plane %d; the RBM is %d x %d" % (x.cols, out.cols, self.n_vis, self.n_hid))
+        with torch.cuda.device(self.device):
+            check(self.lib.kurbm_half_step_vh(self.ctx.handle, C.byref(self.params), x.ptr(row_start), int(rows), x.ld, int(act),
+                                              NOISE_NONE, None, None, out.ptr(out_row), out.ld, self._stream()))
+        return out
+
+    def backprop_workspace(self, rows, n_in=None):
+        """Scratch of backprop_layer for batches of <= rows (kurbm_backprop_workspace_bytes); n_in = 1: of backprop_delta."""
+        n = int(self.lib.kurbm_backprop_workspace_bytes(self.ctx.handle, int(rows), self.n_vis if n_in is None else int(n_in), self.n_hid))
+        if n == 0:
+            raise _lib.KurbmError("kurbm_backprop_workspace_bytes failed")
+        return self._alloc_bytes(n, "backprop_workspace", zero=False)
+
+    def _backprop_ws(self, rows):
+        have = self._ws_bp
+        if have is None or rows > have[0]:
+            have = self._ws_bp = (rows, self.backprop_workspace(rows))
+        return have[1]
+
+    def backprop_delta(self, e, x_out, act, rows=None, in_place=False, ws=None):
+        """The activation-derivative site alone (kurbm_backprop_delta, test hook): delta = e * act'(x_out) for DeviceMatrix e and
+        x_out [rows, n_hid], and db_h = its column sums.  in_place: delta is written over e.  Returns (delta, db_h device tensor)."""
+        rows = e.rows if rows is None else int(rows)
+        with torch.cuda.device(self.device):
+            ws = self.backprop_workspace(rows, 1) if ws is None else ws
+            delta = e if in_place else self._alloc_out(rows, self.n_hid, "bp_delta")
+            db_h = self._alloc_floats(self.n_hid, "bp_db_h", zero=False)
+            check(self.lib.kurbm_backprop_delta(self.ctx.handle, e.ptr(), e.ld, x_out.ptr(), x_out.ld, rows, self.n_hid, int(act),
+                                                delta.ptr(), delta.ld, db_h.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
+        return delta, db_h
+
+    def backprop_layer(self, act, x_in, x_out, e, rows=None, row_start=0, e_in=None, ws=None):
+        """This layer's share of a backward pass (kurbm_backprop_layer): x_in rows [row_start, +rows) of a DeviceMatrix [*, n_vis];
+        x_out and e the first `rows` rows of DeviceMatrix planes with >= n_hid columns (x_out as probs_into left it; e holds
+        dL/dx_out and is OVERWRITTEN with delta); e_in (DeviceMatrix [>= rows, n_vis] or None) receives dL/dx_in.  The packed
+        [dW | db_h | db_v = 0] sums land in this engine's delta buffer, which is returned.  Nothing is applied."""
+        rows = e.rows if rows is None else int(rows)
+        with torch.cuda.device(self.device):
+            ws = self._backprop_ws(rows) if ws is None else ws
+            delta = self.delta_buffer()
+            check(self.lib.kurbm_backprop_layer(self.ctx.handle, C.byref(self.params), int(act), x_in.ptr(row_start), x_in.ld,
+                                                x_out.ptr(), x_out.ld, e.ptr(), e.ld, rows, delta.data_ptr(),
+                                                e_in.ptr() if e_in is not None else None, e_in.ld if e_in is not None else 0,
+                                                ws.data_ptr(), ws.numel(), self._stream()))
+        return delta
+
+    def disc_backprop(self, v, n_labels, rows=None, row_start=0, e_in=None, want_nll=False, ws=None):
+        """The top label RBM's share (kurbm_disc_backprop): the launches of class_grad on rows [row_start, +rows) of DeviceMatrix v
+        [*, n_vis] (label block last) into this engine's delta buffer, then e_in (DeviceMatrix [>= rows, n_pix] or None) =
+        g.W[:n_pix]^T.  Nothing is applied.  Returns (delta, nll): nll a device tensor whose element 0 is the batch's mean
+        -log p(y | v), or None without want_nll."""
+        if v.cols != self.n_vis:
+            raise ValueError("input has %d columns, expected %d (pixels and labels)" % (v.cols, self.n_vis))
+        rows = v.rows - row_start if rows is None else int(rows)
+        with torch.cuda.device(self.device):
+            ws = self._disc_ws(rows, n_labels, v.ld) if ws is None else ws
+            delta = self.delta_buffer()
+            nll = self._alloc_floats(1, "nll_mean", zero=False) if want_nll else None
+            check(self.lib.kurbm_disc_backprop(self.ctx.handle, C.byref(self.params), int(n_labels), v.ptr(row_start), rows, v.ld,
+                                               delta.data_ptr(), e_in.ptr() if e_in is not None else None,
+                                               e_in.ld if e_in is not None else 0, nll.data_ptr() if want_nll else None,
+                                               ws.data_ptr(), ws.numel(), self._stream()))
+        return delta, nll
 
     def score_x3(self, v, rows, row_start, seed, step, mode, chain, planes=None):
         """mean |F(v) - F(v')| of rows [row_start, +rows) of v, v' a fresh one-step reconstruction (rbm.py:225-233), in ONE
