@@ -25,7 +25,7 @@ static inline uint32_t inv_of(int nkt) { return nkt > 1 ? (uint32_t)(0x100000000
 
 // every k_gemm_pb launch: how its blocks are mapped to tiles (two knobs), then the launch
 static hipError_t launch_pb(const kurbm_ctx* ctx, int epi, GemmArgsB& g, hipStream_t st) {
-    g.xcd2d = knob(ctx, KN_X3_XCD2D); g.map_force = knob(ctx, KN_MAP_SLOW);
+    g.xcd2d = knob(ctx, KN_X3_XCD2D); g.map_force = knob(ctx, KN_MAP_SLOW); g.packed_epi = knob(ctx, KN_X3_PACKED_EPI) != 0;
     return launch_gemm_pb(epi, g, st);
 }
 

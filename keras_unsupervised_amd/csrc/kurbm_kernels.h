@@ -401,6 +401,8 @@ struct GemmArgsB {
     const uint16_t* baseA;
     uint32_t offA0, offA1;
     int side;             // k_gemm_pb: some test plane (prob_f32 / out_u) is requested
+    int packed_epi;       // caller: ctx knob KURBM_X3_PACKED_EPI; the launcher clears it wherever the packed epilogue does not apply -- it takes
+                          // a sigmoid Bernoulli half step on a byte A plane that leaves BOTH byte planes (out_bytes, outT_f8) and nothing in fp32
     int pb_max;           // k_gemm_pb: most B pieces any segment multiplies (3: x3; 1: the rounded-bf16 path)
     int cfg;              // 0: 128 x 128 tile; 2: 256 x 64 (half steps)
     // half-step epilogue

@@ -38,6 +38,14 @@
 // transpose across lanes (v_permlane32_swap / v_permlane16_swap): fp8 or k-permuted bytes for a 0/1 sample, three negated bf16 pieces
 // for h_neg; only the row-major plane (bytes of a 0/1 sample, else bf16 pieces) takes a trip through LDS.  RP: also the softplus row
 // sums of F(v) from the same accumulators (the score), by DPP adds.
+// PACKED (Bernoulli draws on a byte A plane, both byte planes wanted and nothing in fp32: h_pos and v_neg of a CD-1 step; ctx knob
+// KURBM_X3_PACKED_EPI, default 1): the sample never becomes a float.  `u < p` sets a byte of a packed dword -- four rows of a lane's
+// column, 0x40 for one; rows past M and columns past N masked once per tile -- and the three outputs come from those 8 dwords: column
+// sums by v_bcnt_u32_b32 and two lane swaps, the transposed plane by the same 4 x 4 lane transpose (fp8 0x38 = pk - (pk >> 3)), the
+// row-major plane by a 4 x 4 BYTE transpose inside each lane quad (DPP quad_perm + v_perm_b32) and one ds_write_b32 per four columns
+// into the patch.  Every other half step (test planes, a persistent chain's fp32 copy, bf16 planes, Gaussian draws, RP) runs the
+// general epilogue, which is also what the packed one is tested against (tests/test_x3_packed_epilogue.py).  Flush of a sampling
+// launch, wave 0, s_memtime stamps: 7 100-7 400 -> 4 300-4 400 cycles, the launches -1.05 us each (profiles/r07_packed_epi_*, LABBOOK.md).
 //
 // Measured (MI355X, config 2, round 4, sustained loops; DESIGN.md section 4, profiles/r04_*): sampling half steps 20.1 / 22.4 us, v -> h
 // prob 21.7, statistics 22.1-22.8 (0.40-0.42 of its MFMA time at the dense peaks), slab reduce + mirrors 9.3; per launch ~2.4 us to
@@ -93,6 +101,25 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ int div_magic(int x, uint32_t inv) { return inv ? (int)__umulhi((uint32_t)x, inv) : x; }
 // (slow = 1: a grid beyond the constants' exact range -- launch_gemm_pb -- pays for the division)
 __device__ __forceinline__ int div_map(int x, int d, uint32_t inv, int slow) { return slow ? x / d : div_magic(x, inv); }
+
+// Sum over the four lanes that share lane & 15 (one per DPP row), the total in every lane: x + (lane ^ 16's x), then that + (lane ^ 32's)
+// -- the pairing and order of `x += __shfl_xor(x, 16); x += __shfl_xor(x, 32)`, so a float sum keeps its bits -- on two lane swaps of the
+// vector ALU.  v_permlane16_swap trades the odd rows of its first operand with the even rows of its second, v_permlane32_swap the upper
+// half of the first with the lower half of the second: of two copies of x, every lane then holds its own value in one result and its
+// partner's in the other.  (As __shfl_xor each step is a ds_bpermute_b32, a dependent round trip through the LDS crossbar.)
+// Every lane of the wave must be active.
+__device__ __forceinline__ uint32_t lanes4_sum(uint32_t x) {
+    auto a = __builtin_amdgcn_permlane16_swap(x, x, false, false);
+    x = a[0] + a[1];
+    auto b = __builtin_amdgcn_permlane32_swap(x, x, false, false);
+    return b[0] + b[1];
+}
+__device__ __forceinline__ float lanes4_sum(float x) {
+    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+    x = __uint_as_float(a[0]) + __uint_as_float(a[1]);
+    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
+}
 
 // Wave-specialised: four LOADER waves beside the eight MFMA waves (768 threads, three waves per SIMD).  The loaders do all
 // the staging in a loop of their own -- LDS-DMA, `buffer_load_dwordx4 ... lds`: no register and no ds_write between memory
@@ -1357,6 +1384,14 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N + 256, (64 * WAVES_M * WAVES
         __syncthreads();                               // (the plane patches reuse this LDS)
     }
     float xv[TM][TN][4];   // the value plane: the sample, or the probability when nothing is drawn
+    // PACKED (g.packed_epi, wave-uniform; the launcher sets it only where it applies): a 0/1 sample whose every output is a byte plane is
+    // never turned into floats.  pk[mi][ni] holds four rows of the lane's column ni, byte r = row rowq + 16 mi + r, 0x40 for one -- the
+    // row-major plane's byte, a single bit for a population count, and 0x38 (fp8 1.0) is pk - (pk >> 3).  Rows past M and columns past N
+    // are masked to zero ONCE, so the column sums and both planes take the dwords as they are; xv is dead on this path.
+    constexpr bool PACKABLE = EPI == EPI_HALFSTEP && NOISE == NOISE_BERNOULLI && AB && !RP;
+    [[maybe_unused]] uint32_t pk[TM][TN];
+    bool packed = false;
+    if constexpr (PACKABLE) packed = g.packed_epi != 0;
     int colb = n0 + wn * WN + l15;
     asm volatile("" : "+v"(colb));   // opaque: keeps the epilogue's address arithmetic out of the k loop's registers
     int rowq = m0 + wm * WM + slot * 4;
@@ -1419,7 +1454,38 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N + 256, (64 * WAVES_M * WAVES
             }
         };
         const bool side = (NOISE == NOISE_BERNOULLI) && g.side;
-        if (!side) {
+        if (packed) {
+            if constexpr (PACKABLE) {
+                // the same pre-activation, sigmoid, uniform and compare as `elementwise`: sample = (u < p) of the GPU's own p
+#pragma unroll
+                for (int ni = 0; ni < TN; ++ni) {
+                    const bool col_ok = colb + ni * 16 < g.N;
+                    const float bias = biasv[ni];
+#pragma unroll
+                    for (int mi = 0; mi < TM; ++mi) {
+                        const uint32_t (&w)[4] = draws[ni * TM + mi];
+                        uint32_t d = 0u;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const float x = 0.5f * acc[mi][ni][r] + bias;   // (the A bytes read as 2.0)
+                            const float p = sigmoidf_fast(x);
+                            const float ua = u32_to_unit(w[r]);
+                            d |= (ua < p) ? (0x40u << (8 * r)) : 0u;
+                        }
+                        pk[mi][ni] = col_ok ? d : 0u;
+                    }
+                }
+                if (m0 + BM > g.M) {   // (wave-uniform) a tile that reaches past the batch: one byte mask per 16-row block
+#pragma unroll
+                    for (int mi = 0; mi < TM; ++mi) {
+                        const int nv = g.M - (rowq + mi * 16);       // rows of this lane's four that exist
+                        const uint32_t mask = nv >= 4 ? 0xFFFFFFFFu : nv <= 0 ? 0u : (1u << (8 * nv)) - 1u;
+#pragma unroll
+                        for (int ni = 0; ni < TN; ++ni) pk[mi][ni] &= mask;
+                    }
+                }
+            }
+        } else if (!side) {
             if (g.act == ACT_SIGMOID) elementwise(std::integral_constant<int, ACT_SIGMOID>{}, std::false_type{});
             else if (g.act == ACT_RELU) elementwise(std::integral_constant<int, ACT_RELU>{}, std::false_type{});
             else elementwise(std::integral_constant<int, ACT_LINEAR>{}, std::false_type{});
@@ -1430,6 +1496,108 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N + 256, (64 * WAVES_M * WAVES
         }
     }
     KURBM_STAMP(ts[3]);
+#ifdef KURBM_STAMPS
+    unsigned long long te[5] = {0, 0, 0, 0, 0};
+#endif
+
+    // ---- the packed flush: column sums, transposed plane and row-major plane of a 0/1 sample from the dwords of pk.  The same bytes
+    // and the same stores as (a), (b) and (d) below write for it (KURBM_X3_PACKED_EPI = 0 runs those instead).
+    if constexpr (PACKABLE) {
+        if (packed) {
+            static_assert(TM == 4 && WM == 64, "packed epilogue: four 16-row blocks per wave, one row of column partials");
+            // (a) ones per column = set bits of the lane's four dwords (v_bcnt_u32_b32 accumulates), added over the four lane groups;
+            //     a small integer, so its float is the sum today's float adds reach
+            if (g.colpart) {
+#pragma unroll
+                for (int ni = 0; ni < TN; ++ni) {
+                    uint32_t cnt = 0u;
+#pragma unroll
+                    for (int mi = 0; mi < TM; ++mi) cnt += (uint32_t)__builtin_popcount(pk[mi][ni]);
+                    cnt = lanes4_sum(cnt);
+                    const int col = colb + ni * 16;
+                    if (slot == 0 && col < g.N)
+                        g.colpart[(size_t)(bm * WAVES_M + wm) * g.ld_colpart + col] = g.colsign * (float)cnt;
+                }
+            }
+#ifdef KURBM_STAMPS
+            KURBM_STAMP(te[0]);
+#endif
+            // (b) transposed plane: the 4 x 4 transpose between block index and lane group of (b) below, on pk itself (k-permuted bytes,
+            //     0x40) or on pk - (pk >> 3) (fp8, 0x38: no borrow between bytes).  Rows past M are pk's zeros.
+            {
+                const bool kp = g.outT_f8 == 2;
+                const int rq16 = rowq + slot * 12;             // m0 + wm WM + 16 slot
+#pragma unroll
+                for (int ni = 0; ni < TN; ++ni) {
+                    const int col = colb + ni * 16;
+                    uint32_t t[4];
+#pragma unroll
+                    for (int mi = 0; mi < 4; ++mi) t[mi] = kp ? pk[mi][ni] : pk[mi][ni] - (pk[mi][ni] >> 3);
+                    {   // (every lane takes part: the swaps sit outside the bounds checks)
+                        auto s0 = __builtin_amdgcn_permlane32_swap(t[0], t[2], false, false);
+                        auto s1 = __builtin_amdgcn_permlane32_swap(t[1], t[3], false, false);
+                        auto s2 = __builtin_amdgcn_permlane16_swap(s0[0], s1[0], false, false);
+                        auto s3 = __builtin_amdgcn_permlane16_swap(s0[1], s1[1], false, false);
+                        t[0] = s2[0]; t[1] = s2[1]; t[2] = s3[0]; t[3] = s3[1];
+                    }
+                    if (col < g.N && rq16 < g.ldoT) {
+                        unsigned char* dst = reinterpret_cast<unsigned char*>(g.outT) + (size_t)col * g.ldoT * 2;
+                        if (kp) {   // (kperm64: eight consecutive k from a multiple of eight stay consecutive)
+                            *reinterpret_cast<u32x2*>(dst + kperm64(rq16)) = u32x2{t[0], t[1]};
+                            *reinterpret_cast<u32x2*>(dst + kperm64(rq16 + 8)) = u32x2{t[2], t[3]};
+                        } else {
+                            *reinterpret_cast<u32x4*>(dst + rq16) = u32x4{t[0], t[1], t[2], t[3]};
+                        }
+                    }
+                }
+            }
+#ifdef KURBM_STAMPS
+            KURBM_STAMP(te[1]);
+#endif
+            // (d) row-major byte plane.  The four lanes of a quad hold four neighbouring columns, four rows each: a 4 x 4 byte transpose
+            //     inside the quad (trade with lane ^ 1, then with lane ^ 2: a DPP move and a v_perm_b32 each) leaves lane j of the quad
+            //     with row j of the four and the quad's four COLUMNS in one dword -- one ds_write_b32 into the patch where there were
+            //     four ds_write_b8.  kperm64 moves whole aligned groups of 8 columns (it leaves the low three bits of a column alone), so
+            //     an aligned group of 4 columns is 4 consecutive patch bytes, dword-aligned in a patch row of a multiple of 4 bytes.
+            //     Columns past N are pk's zeros.
+            {
+                constexpr int PROWB = BN + 16;
+                static_assert(PROWB % 4 == 0 && WN % 16 == 0, "packed epilogue: dword-aligned groups of four columns in the byte patch");
+                static_assert(kperm64(4) == 4 && kperm64(7) == 7 && kperm64(12) == kperm64(8) + 4, "kperm64 keeps aligned groups of four columns together");
+                const int j = l15 & 3;
+                const uint32_t sel1 = (j & 1) ? 0x03070105u : 0x06020400u;   // {neighbour | own}: bytes (n1, o1, n3, o3) / (o0, n0, o2, n2)
+                const uint32_t sel2 = (j & 2) ? 0x03020706u : 0x05040100u;   // (n2, n3, o2, o3) / (o0, o1, n0, n1)
+                unsigned char* prow = smem + (wm * WM + slot * 4 + j) * PROWB;
+#pragma unroll
+                for (int ni = 0; ni < TN; ++ni) {
+                    const int pc = kperm64(wn * WN + ni * 16 + (l15 & ~3));
+#pragma unroll
+                    for (int mi = 0; mi < TM; ++mi) {
+                        uint32_t d = pk[mi][ni];
+                        d = __builtin_amdgcn_perm((uint32_t)__builtin_amdgcn_mov_dpp((int)d, 0xB1, 0xF, 0xF, true), d, sel1);   // quad_perm [1,0,3,2]
+                        d = __builtin_amdgcn_perm((uint32_t)__builtin_amdgcn_mov_dpp((int)d, 0x4E, 0xF, 0xF, true), d, sel2);   // quad_perm [2,3,0,1]
+                        *reinterpret_cast<uint32_t*>(prow + mi * 16 * PROWB + pc) = d;
+                    }
+                }
+                __syncthreads();
+                constexpr int CHB = BN / 16;   // 16-B chunks per row
+                unsigned char* plane = reinterpret_cast<unsigned char*>(g.out);
+#pragma unroll
+                for (int q8 = 0; q8 < (BM * CHB + NT - 1) / NT; ++q8) {
+                    const int q = q8 * NT + tid, row = q / CHB, c = q % CHB;
+                    const int gr = m0 + row, gc = n0 + 16 * c;
+                    if (row < BM && gr < g.M && gc < g.ldo_cols)
+                        *reinterpret_cast<u32x4*>(plane + (size_t)gr * g.ldo + gc) = *reinterpret_cast<const u32x4*>(smem + row * PROWB + 16 * c);
+                }
+            }
+            KURBM_STAMP(ts[4]);
+#if defined(KURBM_STAMPS) && !defined(KURBM_STAMPS_LOOP)
+            tu[0] = te[0] - ts[3]; tu[1] = te[1] - te[0]; tu[2] = 0; tu[3] = 0; tu[4] = ts[4] - te[1]; tu[5] = 0;
+#endif
+            KURBM_STAMP_OUT();
+            return;
+        }
+    }
 
     // (a) column sums of the value plane over this wave's WM rows of the tile: row (bm * WAVES_M + wm) of colpart
     if (g.colpart) {
@@ -1441,8 +1609,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N + 256, (64 * WAVES_M * WAVES
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     if (rowq + mi * 16 + r < g.M) cs += xv[mi][ni][r];
-            cs += __shfl_xor(cs, 16);
-            cs += __shfl_xor(cs, 32);
+            cs = lanes4_sum(cs);   // (cs + lane ^ 16's, then + lane ^ 32's: the pairing of the two __shfl_xor adds this replaces)
             const int col = colb + ni * 16;
             // (the host lays colpart out as one row per 64 rows of the tile: a wave that covers more writes its sum to the
             //  first of its rows and zeros to the others)
@@ -1458,7 +1625,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N + 256, (64 * WAVES_M * WAVES
     }
 
 #ifdef KURBM_STAMPS
-    unsigned long long te[5] = {0, 0, 0, 0, 0};
     KURBM_STAMP(te[0]);
 #endif
     // (b) transposed bf16 plane(s) [N][ldoT]: 4 consecutive rows of this lane's column = one 8-byte store;
@@ -1726,6 +1892,9 @@ hipError_t launch_gemm_pb(int epi, const GemmArgsB& g_in, hipStream_t st) {
         g.offA0 = g.offA1 = 0u; g.offB0 = (uint32_t)ob0; g.offB1 = (uint32_t)ob1;
     }
     g.side = (g.prob_f32 != nullptr) || (g.out_u != nullptr);
+    // the packed epilogue (k_gemm_pb, "PACKABLE"): only where every output of the half step is a byte plane of the 0/1 sample
+    g.packed_epi = (g.packed_epi && epi == EPI_HALFSTEP && g.noise == NOISE_BERNOULLI && g.act == ACT_SIGMOID && g.a_bytes && !g.rp &&
+                    g.out && g.out_bytes && g.outT && g.outT_f8 && !g.side && !g.out_f32) ? 1 : 0;
     const int nblk = g.grid_m * g.grid_n * g.nsplit;
     {   // XCD blocks: the factorisation 8 = xz * xr * xc (xz | nsplit, xr | grid_m, xc | grid_n) with the fewest operand rows
         // per XCD, weighted by the tiles a k-tile loads (one A tile per segment, npb B tiles)
