@@ -89,6 +89,9 @@ static int half_step_b(kurbm_ctx* ctx, int layout, const kurbm_params* p, const 
     g.nkt = g.K / 64;
     g.inv_nkt = inv_of(g.nkt);
     g.kt_total = g.nseg * g.nkt; g.kt_per_split = g.kt_total; g.nsplit = 1;
+    // the units end in the first k-step of the last k-tile (784 visibles: 24.5 k-steps of 32 in 13 tiles): its second k-step is padding
+    // in both operands, and the byte-plane walk does not multiply it (launch_gemm_pb clears the flag for every other walk)
+    g.k_tail = (knob(ctx, KN_X3_KTAIL) != 0 && round_up(vh ? p->n_vis : p->n_hid, 32) < g.K) ? 1 : 0;
     g.bias = vh ? p->b_h : p->b_v;
     g.act = act; g.noise = noise;
     if (rng) g.rng = *rng;

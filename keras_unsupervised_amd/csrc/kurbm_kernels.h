@@ -354,7 +354,9 @@ struct GemmArgsB {
     // ---- the WALK: everything a wave reads between its first instruction and its first request for data comes first and
     // together (three 64-byte lines of the argument segment): the scalar loads of the kernel's entry are then a few wide
     // ones, not a chain of narrow ones -- each costs its latency even when it hits the scalar cache (DESIGN.md section 4,
-    // round 3, "the entry of a launch")
+    // round 3, "the entry of a launch").  A LOADER wave of k_gemm_pb waits for these three lines ONLY before its first request
+    // (the kernel asserts that the block ends at `B0`, within 192 bytes): a field that a loader's way to its first request reads
+    // belongs in here, and a field it does not read belongs behind (`a_tr`, which only the paired statistics walk reads, stayed behind)
     const uint16_t* A0;
     const uint16_t* A1;
     // filled by launch_gemm_pb: one buffer descriptor per operand (base = the lower of the two sets'
@@ -404,6 +406,8 @@ struct GemmArgsB {
     int packed_epi;       // caller: ctx knob KURBM_X3_PACKED_EPI; the launcher clears it wherever the packed epilogue does not apply -- it takes
                           // a sigmoid Bernoulli half step on a byte A plane that leaves BOTH byte planes (out_bytes, outT_f8) and nothing in fp32
     int pb_max;           // k_gemm_pb: most B pieces any segment multiplies (3: x3; 1: the rounded-bf16 path)
+    int k_tail;           // caller (half steps): the second k-step of the LAST k-tile lies wholly in the k padding (zeros in both operands) --
+                          // the three-piece byte-plane walk then runs that tile's first k-step only; the launcher clears it for every other walk
     int cfg;              // 0: 128 x 128 tile; 2: 256 x 64 (half steps)
     // half-step epilogue
     const float* bias;

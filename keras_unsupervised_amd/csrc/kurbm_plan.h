@@ -28,7 +28,7 @@ inline void tile_shape(int cfg, int* bm, int* bn) {
 // planner decide".
 enum { KN_LDPAD, KN_X3_F8POS, KN_X3_BYTES, KN_X3_STATS_TALL, KN_BF16_SPLIT, KN_X3_FULL, KN_X3_TALL, KN_X3_MFAST, KN_X3_STATS_MFAST,
        KN_UNFUSED_MIRROR, KN_X3_XCD2D, KN_REDUCE_TR, KN_DP_CHUNKS, KN_X3_STATS_BYTES, KN_MAP_SLOW, KN_X3_PAIR, KN_X3_SPLIT_STATS, KN_X3_ATR, KN_SMALL_LOCAL,
-       KN_DISC_STAGE, KN_X3_PACKED_EPI, KN_CFG_VH, KN_CFG_HV, KN_CFG_OUTER, KN_SPLIT, KN_TILE_MAJOR, KN_COUNT };
+       KN_DISC_STAGE, KN_X3_PACKED_EPI, KN_X3_KTAIL, KN_CFG_VH, KN_CFG_HV, KN_CFG_OUTER, KN_SPLIT, KN_TILE_MAJOR, KN_COUNT };
 constexpr int KN_AUTO = -1;
 struct KnobRow { const char* env; int dflt; };
 inline constexpr KnobRow KNOBS[KN_COUNT] = {
@@ -62,6 +62,8 @@ inline constexpr KnobRow KNOBS[KN_COUNT] = {
                                    //    its slab reduction and k_class_reduce.  kurbm_disc_step / kurbm_disc_epoch do not read it
     {"KURBM_X3_PACKED_EPI", 1},    // 0: a Bernoulli half step that leaves byte planes builds them from fp32 1.0 / 0.0 per element (the general
                                    //    epilogue of k_gemm_pb); 1: from packed bytes, four rows of a column per dword (the same planes, bit for bit)
+    {"KURBM_X3_KTAIL", 1},         // 0: a half step on a byte A plane multiplies the whole last k-tile; 1: where the units end in the tile's first
+                                   //    k-step (round_up(n, 32) < round_up(n, 64): 784 visibles) the second one, all padding, is skipped (exact)
     {"KURBM_CFG_VH", KN_AUTO},     // fp32 path: the tile configuration (CFG_*) of the v -> h half steps,
     {"KURBM_CFG_HV", KN_AUTO},     // ... of the h -> v half steps,
     {"KURBM_CFG_OUTER", KN_AUTO},  // ... of the statistics GEMM (these three in the order of LAYOUT_*)

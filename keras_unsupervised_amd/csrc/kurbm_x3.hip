@@ -30,8 +30,14 @@
 //   everything else                    the generic two-stage walk of a tile list (segments of one to three pieces: KURBM_X3_PAIR=0,
 //                                      KURBM_X3_SPLIT_STATS=0, the free-energy GEMM of real-valued data, fp8 positive statistics on
 //                                      bf16 planes)
-// Entry: the argument segment warmed in one batch (kurbm_device.h), block mapping by multiply-high constants into XCD-aware 2-D
-// blocks, the loaders at high priority until their first requests are out.
+// Entry: the ROLES PART FIRST, on the wave index alone; each role then warms the argument lines it will read (kurbm_device.h: a loader the
+// three WALK lines of GemmArgsB, an MFMA wave the whole segment), maps its block by multiply-high constants into XCD-aware 2-D blocks and
+// runs only its own set-up -- a loader its staging offsets, descriptors and first tile reference (on the byte-plane walks straight from
+// the arguments, scalar), an MFMA wave its accumulators, bias, draw counters and, where its walk decodes tiles, the walk table.  The
+// loaders stay at high priority until their first requests are out.
+// The k tail of a half step on a byte plane (ctx knob KURBM_X3_KTAIL, default 1): where the units end in the first k-step of the last
+// k-tile (784 visibles: 24.5 k-steps of 32), that tile runs its first k-step only -- 24 MFMAs per wave less in the one tile that has no
+// successor to hide behind; exact (tests/test_x3_k_tail.py).
 //
 // Epilogue of a half step, from registers: bias + activation + Philox draw (the words of a lane's first columns drawn in the prologue
 // and parked in LDS); column sums of the value plane (bias statistics); the transposed plane(s) in 16-byte stores after a 4 x 4
@@ -56,6 +62,7 @@
 // (statistics); the split is an implementation choice of this build.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -215,8 +222,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N + 256, (64 * WAVES_M * WAVES
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool loader = wave >= NT / 64;                // wave-uniform role
-    // Every wave runs the same ~600 instructions of set-up (block mapping, operand offsets, descriptors) before the roles part,
-    // three waves to a SIMD; what the launch waits for is the loaders' first requests.  They go first until those are out.
+    // What the launch waits for is the loaders' first requests: they go first, three waves to a SIMD, until those are out (and run
+    // nothing on the way that is not theirs: `enter`, at the role branch).
     if (KURBM_PRIO_ENTRY && loader) __builtin_amdgcn_s_setprio(KURBM_PRIO_ENTRY);
     const int stid = tid & 255;                         // loader thread id
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
@@ -263,43 +270,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N + 256, (64 * WAVES_M * WAVES
 #define KURBM_LSTAMP_OUT() do { } while (0)
 #endif
 
-    warm_kernel_arguments<sizeof(GemmArgsB)>();
-    KURBM_PSTAMP(3);
-    const int nwg = gridDim.x;
-    int bid = blockIdx.x;
-    int z, bm, bn;
-    if (g.xcd_r) {
-        // workgroup i runs on XCD i % 8: XCD (xz, xr, xc) owns k slices [xz zl, +zl), row tiles [xr rl, +rl), column tiles [xc cl, +cl)
-        const int xcd = bid & 7, idx = bid >> 3;
-        const int xz = xcd >> g.map_lrc, xr = (xcd & ((1 << g.map_lrc) - 1)) >> g.map_lxc, xc = xcd & ((1 << g.map_lxc) - 1);
-        const int rl = g.map_rl, cl = g.map_cl;
-        const int zi = div_map(idx, rl * cl, g.map_inv_a, g.map_slow), t2 = idx - zi * (rl * cl);
-        const int q2 = div_map(t2, g.m_fastest ? rl : cl, g.map_inv_b, g.map_slow);   // t2 / rl (m fastest) or t2 / cl
-        const int ri = g.m_fastest ? t2 - q2 * rl : q2;
-        const int ci = g.m_fastest ? q2 : t2 - q2 * cl;
-        z = xz * g.map_zl + zi; bm = xr * rl + ri; bn = xc * cl + ci;
-    } else {
-        {   // XCD-aware bijective remap (see kurbm_kernels.hip)
-            const int xcd = bid & 7, q = nwg >> 3, rr = nwg & 7;
-            bid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
-        }
-        const int tiles_mn = g.grid_m * g.grid_n;
-        z = div_map(bid, tiles_mn, g.map_inv_a, g.map_slow);
-        const int tmn = bid - z * tiles_mn;
-        const int q2 = div_map(tmn, g.m_fastest ? g.grid_m : g.grid_n, g.map_inv_b, g.map_slow);   // tmn / grid_m (m fastest) or tmn / grid_n
-        bm = g.m_fastest ? tmn - q2 * g.grid_m : q2;
-        bn = g.m_fastest ? q2 : tmn - q2 * g.grid_n;
-    }
-    const int m0 = bm * BM, n0 = bn * BN;
-    KURBM_PSTAMP(4);
-
-    const int t_begin = z * g.kt_per_split;
-    int t_end = t_begin + g.kt_per_split;
-    if (t_end > g.kt_total) t_end = g.kt_total;
-    // (a half-step tile that lies wholly in the column padding of its row-major plane has nothing to multiply: it only
-    //  writes that plane's zeros)
-    const int nt = (t_end > t_begin && !(EPI == EPI_HALFSTEP && n0 >= g.N)) ? t_end - t_begin : 0;
-
+    // Block mapping, k range and the walk's kind: computed by `enter`, which each role runs for itself behind the role branch
+    int z, bm, bn, m0, n0, t_begin, t_end, nt;
     // Staging map of the loader waves.  A wave instruction of LDS-DMA writes 1 KiB of LDS linearly (lane l -> bytes
     // 16 l ...): piece q = 8 rows of a tile, lane l fills chunk slot l % 8 of row 8 q + l / 8.  The swizzle therefore
     // sits on the SOURCE: the lane that fills slot ch of a row fetches chunk ch ^ key(row) of that row, the same
@@ -312,33 +284,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N + 256, (64 * WAVES_M * WAVES
     // ((r >> 2) & 3)) (cdna_hip_programming.md T10, image (b)), and the MFMA waves fetch their fragments with ds_read_b64_tr_b16: a lane
     // needs 8 consecutive k of ONE m, i.e. a column of that image.
     constexpr bool ATR = BSP && EPI == EPI_SLAB;
-    const bool a_tr = ATR && g.a_tr != 0;
-    unsigned goffA[NA], goffB[NB1];
-#pragma unroll
-    for (int it = 0; it < NA; ++it) {
-        const int q = it * NTS + stid, row = q / CPR, ch = q % CPR;
-        const int x = (m0 + row < g.M) ? m0 + row : 0;
-        // (a byte plane has lda BYTES between its rows; its 128-byte row piece is 128 k)
-        goffA[it] = AB ? (unsigned)(x * g.lda + 16 * (ch ^ ((row >> 1) & 7))) : 2u * (unsigned)(x * g.lda + 8 * (ch ^ ((row >> 1) & 7)));
-        if (a_tr) {   // row = k index inside the tile (16 chunks of 8 m per row); rows and columns past the matrix are the plane's zero padding
-            const int rt = q >> 4, ct = q & 15;
-            goffA[it] = 2u * (unsigned)(rt * g.lda + m0 + 8 * (ct ^ (((rt & 3) << 2) | ((rt >> 2) & 3))));
-        }
-    }
-#pragma unroll
-    for (int it = 0; it < NB1; ++it) {
-        const int q = it * NTS + stid, row = q / CPR, ch = q % CPR;
-        const int x = (n0 + row < g.N) ? n0 + row : 0;
-        goffB[it] = 2u * (unsigned)(x * g.ldb + 8 * (ch ^ ((row >> 1) & 7)));
-    }
-    typedef __amdgpu_buffer_rsrc_t rsrc_t;
-    // B: one descriptor for both operand sets (they live in one workspace), a set is a scalar offset.  A: one descriptor
-    // PER SET -- set 0 of the statistics GEMM (the v_pos planes) may sit in the caller's resident data planes, any distance
-    // from the workspace that holds set 1 -- picked per tile by a scalar select.
-    [[maybe_unused]] const rsrc_t dA0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(g.A0), 0, 0xFFFFFFFF, 0x00020000);
-    [[maybe_unused]] const rsrc_t dA1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(g.A1 ? g.A1 : g.A0), 0, 0xFFFFFFFF, 0x00020000);
-    [[maybe_unused]] const rsrc_t dB = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(g.baseB), 0, 0xFFFFFFFF, 0x00020000);
-
+    bool a_tr;                                 // (enter)
     // a tile: the scalar byte offsets of its A rows and of piece 0 of its B rows
     struct TileRef { uint32_t oa, ob, bplane, oa_piece; int npb; bool neg, f8; };
     constexpr bool F8 = (EPI == EPI_SLAB && PB == 3);   // the kernel that may meet fp8 tiles (g.f8pos)
@@ -350,17 +296,19 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N + 256, (64 * WAVES_M * WAVES
     // reference five scalar instructions.  (Until round 3 every tile was decoded from its index in BOTH loops -- two multiply-
     // highs, 64-bit shifts, a dozen kernel arguments kept live in scalar registers that then spilled: a sixth of the k loop.)
     struct Walk { int a, b; };
-    const bool wl_f8 = F8 && g.f8pos, wl_sf = g.seg_fastest != 0;
-    const int wl_len = wl_f8 ? 2 * g.nseg - 1 : wl_sf ? g.nseg : g.nkt;
-    uint32_t t_code, t_oa, t_ob, t_bp;
-    {
+    bool wl_f8, wl_sf;                         // (enter)
+    int wl_len;
+    // (built behind the role branch, and only by the walks that decode tiles: the byte-plane walks take their references from
+    //  the arguments -- seg_ref -- and never read it)
+    uint32_t t_code = 0u, t_oa = 0u, t_ob = 0u, t_bp = 0u;
+    auto walk_table = [&]() __attribute__((always_inline)) {
         const int sl = lane < g.nseg ? lane : 0;
         t_code = (uint32_t)(g.seg_codes >> (5 * sl)) & 31u;
         const bool ng = (t_code & 16u) != 0u;
         t_oa = 2u * (t_code & 3u) * (uint32_t)(ng ? g.a_plane1 : g.a_plane0);
         t_ob = ng ? g.offB1 : g.offB0;
         t_bp = 2u * (uint32_t)(ng ? g.b_plane1 : g.b_plane0);
-    }
+    };
     auto walk_at = [&](int t) __attribute__((always_inline)) {   // (one multiply-high: outside the loops)
         const uint32_t inv = (wl_f8 || wl_sf) ? g.inv_nseg : g.inv_nkt;      // (0: the period is one tile long)
         Walk w;
@@ -396,12 +344,24 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N + 256, (64 * WAVES_M * WAVES
         return r;
     };
     auto tile_of = [&](int t) __attribute__((always_inline)) { return walk_ref(walk_at(t)); };
+    // Tile `kt` of segment `seg` (a constant) straight from the arguments, all scalar: what walk_ref reads out of the table.  The first
+    // reference of a loader on a byte-plane walk -- one segment, or the fixed unit of the statistics -- is a shift, two selects and a
+    // multiply-add on its k slice: no table, no v_readlane on the way to the first request.
+    auto seg_ref = [&](int seg, int kt, bool f8 = false) __attribute__((always_inline)) {
+        TileRef r;
+        const uint32_t code = (uint32_t)(g.seg_codes >> (5 * seg)) & 31u;
+        const uint32_t k0 = 2u * (uint32_t)(kt * BKB);
+        r.neg = (code & 16u) != 0u;
+        r.oa = 2u * (code & 3u) * (uint32_t)(r.neg ? g.a_plane1 : g.a_plane0) + k0;
+        r.oa_piece = code & 3u;
+        r.f8 = f8;
+        r.ob = (r.neg ? g.offB1 : g.offB0) + k0;
+        r.bplane = 2u * (uint32_t)(r.neg ? g.b_plane1 : g.b_plane0);
+        r.npb = (int)((code >> 2) & 3u);
+        return r;
+    };
 
     f32x4 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     typedef u32x4 afrag;   // (AB: fa[0] = the 16 bytes of BOTH k-steps of a tile, expanded per k-step into fx; fa[1] unused)
     afrag fa[2][TM];
@@ -410,7 +370,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N + 256, (64 * WAVES_M * WAVES
     const int swz = (l15 >> 1) & 7;
     // AB: `ablk` = the block buffer (0 / 1) of the tile pair in work; tile `buf` (= its parity) is half `buf` of the block's k
     int ablk = 0;
-    const bool bsp = BSP && g.bshare == 2;     // (wave-uniform) the paired walk: A stages and B stages apart
+    bool bsp;                                  // (enter; wave-uniform) the paired walk: A stages and B stages apart
     auto frag_a = [&](int buf, int ks, afrag (&f)[TM], int blk_step = 0) __attribute__((always_inline)) {
         if constexpr (AB) {   // tile `buf` of the block, lane group `slot`: chunk 4 buf + slot of the 128-byte row (k-permuted plane)
             if (ks == 0) {
@@ -490,12 +450,18 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N + 256, (64 * WAVES_M * WAVES
     // (cur = the tile's B stage; half = its half of the A block, AB only -- with two stages the two coincide)
     // (bcur / anext_ / bnext_ >= 0: the B stage of this tile and the A / B stages of the next one, where they are not `cur` and
     //  `cur + 1` -- the shared-B walk)
-    auto one_tile = [&](const int cur, const int half, auto npb_tag, const int bcur_ = -1, const int anext_ = -1,
-                        const int bnext_ = -1) __attribute__((always_inline)) {
+    // TAIL (tail_tag; three pieces on a byte A plane, g.k_tail): the LAST tile of a k range whose second k-step lies wholly in the k
+    // padding -- zeros in both operands, and the accumulators started at +0 -- runs its first k-step only: three micro-steps, the B
+    // fragments of that k-step, no second expansion, and nothing read behind its barrier (no tile follows).  The loaders stage the
+    // whole tile all the same (their piece counts are what the counted waits rest on), and the barrier stays: they count tiles.
+    auto tile_body = [&](const int cur, const int half, auto npb_tag, const int bcur_, const int anext_, const int bnext_,
+                         auto tail_tag) __attribute__((always_inline)) {
         const int acur = AB ? half : cur, anext = anext_ >= 0 ? anext_ : AB ? (half ^ 1) : (cur + 1) % NSTG;
         const int bcur = bcur_ >= 0 ? bcur_ : cur, bnext = bnext_ >= 0 ? bnext_ : (cur + 1) % NSTG;
         constexpr int NPB = decltype(npb_tag)::value;
-        constexpr int NU = KS * NPB;
+        constexpr bool TAIL = decltype(tail_tag)::value;
+        static_assert(!TAIL || (AB && NPB == 3), "the tail tile: three pieces on a byte A plane");
+        constexpr int NU = TAIL ? NPB : KS * NPB;
 #ifdef KURBM_STAMPS
         unsigned long long tq[7];
         KURBM_STAMP(tq[0]);
@@ -508,20 +474,22 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N + 256, (64 * WAVES_M * WAVES
                 // fragments are read TWO micro-steps ahead (an LDS read under load takes longer than the 8 MFMAs
                 // of one micro-step); the tile is entered with fa[0], fb[0] loaded, so u = 0 catches up
                 if (u == 0) { frag_b(bcur, 0, 1, fb[1]); frag_b(bcur, 0, 2, fb[2]); }
-                if (u == 1) { frag_a(acur, 1, fa[1]); frag_b(bcur, 1, 0, fb[0]); }
-                if (u == 2) frag_b(bcur, 1, 1, fb[1]);
-                if (u == 3) frag_b(bcur, 1, 2, fb[2]);
+                if (!TAIL && u == 1) { frag_a(acur, 1, fa[1]); frag_b(bcur, 1, 0, fb[0]); }
+                if (!TAIL && u == 2) frag_b(bcur, 1, 1, fb[1]);
+                if (!TAIL && u == 3) frag_b(bcur, 1, 2, fb[2]);
                 // The tile's ONLY barrier sits in front of its last micro-step (behind it the loaders may refill this
                 // stage), and the next tile's first fragments are read right behind it, under the MFMAs of micro-step 5
                 // instead of in front of an idle matrix pipe.  (The barrier behind micro-step 3: no faster, LABBOOK.)
                 if (u == NU - 1) {
                     __syncthreads();
                     __builtin_amdgcn_sched_barrier(0);
-                    frag_a(anext, 0, fa[0], acur);   // (AB: after the second tile of a pair comes the other block)
-                    frag_b(bnext, 0, 0, fb[0]);
+                    if (!TAIL) {
+                        frag_a(anext, 0, fa[0], acur);   // (AB: after the second tile of a pair comes the other block)
+                        frag_b(bnext, 0, 0, fb[0]);
+                    }
                 }
                 mfmas(fa[ks & 1], fb[u % 3]);
-                if (AB && (u + 1) % NPB == 0) {   // the NEXT k-step's, behind this step's MFMAs (same registers: not among them)
+                if (AB && !TAIL && (u + 1) % NPB == 0) {   // the NEXT k-step's, behind this step's MFMAs (same registers: not among them)
                     __builtin_amdgcn_sched_barrier(0);
                     expand_a(((u + 1) / NPB) & 1);
                 }
@@ -552,6 +520,10 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N + 256, (64 * WAVES_M * WAVES
 #endif
         }
         __builtin_amdgcn_sched_barrier(0);
+    };
+    auto one_tile = [&](const int cur, const int half, auto npb_tag, const int bcur_ = -1, const int anext_ = -1,
+                        const int bnext_ = -1) __attribute__((always_inline)) {
+        tile_body(cur, half, npb_tag, bcur_, anext_, bnext_, std::false_type{});
     };
     // The second tile of a k position on the paired walk (BSP): (A piece 1) x (B pieces 0, 1) and (A piece 2) x (B piece 0), 2 x 3 micro-
     // steps of 8 MFMAs like a three-piece tile.  Entered with fa[0] = A1 and fb[0] = B0 of k-step 0 (the tile in front read them
@@ -644,15 +616,87 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N + 256, (64 * WAVES_M * WAVES
                               g.rng.seed_lo, g.rng.seed_hi, w);
             }
     };
-    float biasv[TN];   // loaded here too: in the epilogue its latency would be exposed
-#pragma unroll
-    for (int ni = 0; ni < TN; ++ni) {
-        const int c = n0 + wn * WN + l15 + ni * 16;
-        biasv[ni] = (EPI == EPI_HALFSTEP && c < g.N) ? g.bias[c] : 0.f;
-    }
-    if (loader) {   // (NOT marked likely: the loaders would reach their first request ~1 000 cycles sooner, but hipcc then treats the
-                    //  MFMA waves' path as cold and their k loop takes 1.5 x the time)
+    float biasv[TN];   // loaded in the prologue (behind the role branch): in the epilogue its latency would be exposed
+    // THE ENTRY.  The roles part first: each runs `enter` -- argument warm-up, block mapping, k range, the walk's kind -- for itself and
+    // then only its own set-up, so that nothing of one role's way can be scheduled into the other's (with the branch behind a common
+    // set-up hipcc hoisted the MFMA waves' argument loads -- bias, counters, planes: lines outside the WALK block -- in front of it, and
+    // the loaders waited for them).  A loader waits for the WALK lines of the argument segment only, all it reads on its way to its
+    // first request; the MFMA waves of the same workgroup touch the rest meanwhile (every line costs a wave that waits for it: LABBOOK
+    // round 4 item 6).
+    constexpr int WALK_BYTES = (int)offsetof(GemmArgsB, B0);
+    static_assert(WALK_BYTES <= 192, "GemmArgsB: the WALK block is three 64-byte lines");
+    auto enter = [&](auto walk_only) __attribute__((always_inline)) {
+        if constexpr (decltype(walk_only)::value) warm_kernel_arguments<WALK_BYTES>();
+        else warm_kernel_arguments<sizeof(GemmArgsB)>();
+        KURBM_PSTAMP(3);
+        const int nwg = gridDim.x;
+        int bid = blockIdx.x;
+        if (g.xcd_r) {
+            // workgroup i runs on XCD i % 8: XCD (xz, xr, xc) owns k slices [xz zl, +zl), row tiles [xr rl, +rl), column tiles [xc cl, +cl)
+            const int xcd = bid & 7, idx = bid >> 3;
+            const int xz = xcd >> g.map_lrc, xr = (xcd & ((1 << g.map_lrc) - 1)) >> g.map_lxc, xc = xcd & ((1 << g.map_lxc) - 1);
+            const int rl = g.map_rl, cl = g.map_cl;
+            const int zi = div_map(idx, rl * cl, g.map_inv_a, g.map_slow), t2 = idx - zi * (rl * cl);
+            const int q2 = div_map(t2, g.m_fastest ? rl : cl, g.map_inv_b, g.map_slow);   // t2 / rl (m fastest) or t2 / cl
+            const int ri = g.m_fastest ? t2 - q2 * rl : q2;
+            const int ci = g.m_fastest ? q2 : t2 - q2 * cl;
+            z = xz * g.map_zl + zi; bm = xr * rl + ri; bn = xc * cl + ci;
+        } else {
+            {   // XCD-aware bijective remap (see kurbm_kernels.hip)
+                const int xcd = bid & 7, q = nwg >> 3, rr = nwg & 7;
+                bid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+            }
+            const int tiles_mn = g.grid_m * g.grid_n;
+            z = div_map(bid, tiles_mn, g.map_inv_a, g.map_slow);
+            const int tmn = bid - z * tiles_mn;
+            const int q2 = div_map(tmn, g.m_fastest ? g.grid_m : g.grid_n, g.map_inv_b, g.map_slow);   // tmn / grid_m (m fastest) or tmn / grid_n
+            bm = g.m_fastest ? tmn - q2 * g.grid_m : q2;
+            bn = g.m_fastest ? q2 : tmn - q2 * g.grid_n;
+        }
+        m0 = bm * BM; n0 = bn * BN;
+        KURBM_PSTAMP(4);
+        t_begin = z * g.kt_per_split;
+        t_end = t_begin + g.kt_per_split;
+        if (t_end > g.kt_total) t_end = g.kt_total;
+        // (a half-step tile that lies wholly in the column padding of its row-major plane has nothing to multiply: it only
+        //  writes that plane's zeros)
+        nt = (t_end > t_begin && !(EPI == EPI_HALFSTEP && n0 >= g.N)) ? t_end - t_begin : 0;
+        a_tr = ATR && g.a_tr != 0;
+        wl_f8 = F8 && g.f8pos; wl_sf = g.seg_fastest != 0;
+        wl_len = wl_f8 ? 2 * g.nseg - 1 : wl_sf ? g.nseg : g.nkt;
+        bsp = BSP && g.bshare == 2;
+    };
+    if (loader) {   // (NOT marked likely: hipcc then treats the MFMA waves' path as cold and their k loop takes 1.5 x the time.  The
+                    //  loaders' body stands FIRST, as it always has, and the MFMA waves' k loop is laid out as before.)
         KURBM_PSTAMP(5);
+        enter(std::true_type{});
+        unsigned goffA[NA], goffB[NB1];
+#pragma unroll
+        for (int it = 0; it < NA; ++it) {
+            const int q = it * NTS + stid, row = q / CPR, ch = q % CPR;
+            const int x = (m0 + row < g.M) ? m0 + row : 0;
+            // (a byte plane has lda BYTES between its rows; its 128-byte row piece is 128 k)
+            goffA[it] = AB ? (unsigned)(x * g.lda + 16 * (ch ^ ((row >> 1) & 7))) : 2u * (unsigned)(x * g.lda + 8 * (ch ^ ((row >> 1) & 7)));
+            if (a_tr) {   // row = k index inside the tile (16 chunks of 8 m per row); rows and columns past the matrix are the plane's zero padding
+                const int rt = q >> 4, ct = q & 15;
+                goffA[it] = 2u * (unsigned)(rt * g.lda + m0 + 8 * (ct ^ (((rt & 3) << 2) | ((rt >> 2) & 3))));
+            }
+        }
+#pragma unroll
+        for (int it = 0; it < NB1; ++it) {
+            const int q = it * NTS + stid, row = q / CPR, ch = q % CPR;
+            const int x = (n0 + row < g.N) ? n0 + row : 0;
+            goffB[it] = 2u * (unsigned)(x * g.ldb + 8 * (ch ^ ((row >> 1) & 7)));
+        }
+        typedef __amdgpu_buffer_rsrc_t rsrc_t;
+        // B: one descriptor for both operand sets (they live in one workspace), a set is a scalar offset.  A: one descriptor
+        // PER SET -- set 0 of the statistics GEMM (the v_pos planes) may sit in the caller's resident data planes, any distance
+        // from the workspace that holds set 1 -- picked per tile by a scalar select.
+        [[maybe_unused]] const rsrc_t dA0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(g.A0), 0, 0xFFFFFFFF, 0x00020000);
+        [[maybe_unused]] const rsrc_t dA1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(g.A1 ? g.A1 : g.A0), 0, 0xFFFFFFFF, 0x00020000);
+        [[maybe_unused]] const rsrc_t dB = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(g.baseB), 0, 0xFFFFFFFF, 0x00020000);
+
+        if constexpr (!AB) walk_table();
         // ---- loader waves: a loop of their own; one barrier per tile, like the MFMA waves.  `buffer_load_dwordx4 ... lds`,
         // one 1-KiB piece (8 rows of a tile) per wave instruction, straight into the stage that the barrier before has
         // freed; the wait for a tile's pieces and then the tile's barrier make them visible to the MFMA waves
@@ -707,7 +751,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N + 256, (64 * WAVES_M * WAVES
                 static_assert(3 * NPT <= 63, "vmcnt");
                 // ONE segment (launch_pb checks): tile t lies 128 t bytes along k in the B operand, block j 128 j bytes in the A
                 // plane -- running scalars, no tile_of in the loop: the loaders' issue is this loop's critical path
-                TileRef rb = tile_of(t_begin);
+                TileRef rb = seg_ref(0, t_begin);
                 TileRef ra = rb;
                 ra.neg = false;
                 const uint32_t ob0 = rb.ob, oa0 = 128u * (uint32_t)(t_begin >> 1);
@@ -773,7 +817,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N + 256, (64 * WAVES_M * WAVES
                 // so the tile's barrier waits for everything but the 10 pieces just requested (a counted vmcnt).
                 static_assert(NA / 2 + 3 * NB1 == 10 && NA + NB1 == 10, "10 pieces per wave and tile");
                 const int nu = nt / 3;
-                TileRef rp = tile_of(t_begin), rn = tile_of(t_begin + 1);
+                // (whole units per slice: tile t_begin is the fp8 tile of unit t_begin / 3, the next one k-tile 2 (t_begin / 3) of segment 1)
+                const int ub = g.inv_nseg ? (int)__umulhi((uint32_t)t_begin, g.inv_nseg) : t_begin;
+                TileRef rp = seg_ref(0, ub, true), rn = seg_ref(1, 2 * ub);
                 TileRef ra = rn;                                 // the byte block: its plane holds 128 k in the 128 bytes a
                 ra.oa = rn.oa >> 1;                              // bf16 plane spends on 64 (piece 0: no plane offset in oa)
                 int bf = 0, bb = 1;                              // A buffers of fp8 block u / byte block u (u = 0)
@@ -826,7 +872,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N + 256, (64 * WAVES_M * WAVES
                 // A block j (128 k of bytes) serves tiles 2 j and 2 j + 1; while tile i is multiplied, the B pieces of tile
                 // i + 1 and HALF of block i / 2 + 1 are requested (its buffer was freed by tile 2 (i / 2) - 1)
                 // (ONE segment -- launch_pb checks: B tile t lies 128 t bytes along k; no tile_of in the loop)
-                TileRef ra = tile_of(t_begin);
+                TileRef ra = seg_ref(0, t_begin);
                 TileRef rb = ra;
                 const uint32_t ob0 = ra.ob;
                 ra.neg = false; ra.oa = 128u * (uint32_t)(t_begin >> 1);   // (a k slice starts on a whole block: launch_pb checks)
@@ -992,6 +1038,18 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N + 256, (64 * WAVES_M * WAVES
             }
         }
         return;
+    }
+    // ---- MFMA waves: their own set-up -- the walk table where their loop decodes tiles, accumulators, bias
+    enter(std::false_type{});
+    if constexpr (!AB) walk_table();
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ni = 0; ni < TN; ++ni) {
+        const int c = n0 + wn * WN + l15 + ni * 16;
+        biasv[ni] = (EPI == EPI_HALFSTEP && c < g.N) ? g.bias[c] : 0.f;
     }
     if constexpr (NI_LDS > 0) {
         if (nt > 0) {
@@ -1195,12 +1253,17 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N + 256, (64 * WAVES_M * WAVES
         } else {
             if constexpr (AB) {
                 // one segment of PB pieces (launch_pb checks): every tile is the same tile -- no tile list, no dispatch
-                for (; i + 1 < nt; i += 2) {
+                // (g.k_tail: all but the last tile, which is a TAIL tile -- in whichever stage and half of its block it falls)
+                constexpr bool KT = PB == 3 && EPI == EPI_HALFSTEP;
+                const int ntf = (KT && g.k_tail) ? nt - 1 : nt;
+                for (; i + 1 < ntf; i += 2) {
                     one_tile(0, 0, std::integral_constant<int, PB>{});
                     one_tile(1, 1, std::integral_constant<int, PB>{});
                     ablk ^= 1;
                 }
-                if (i < nt) one_tile(0, 0, std::integral_constant<int, PB>{});
+                if (i < ntf) { one_tile(0, 0, std::integral_constant<int, PB>{}); ++i; }
+                if constexpr (KT)
+                    if (i < nt) tile_body(i & 1, i & 1, std::integral_constant<int, PB>{}, -1, -1, -1, std::true_type{});
             } else {
                 if (bsp) {
                     // (see the loaders) k position kt: one three-piece tile on A stage (3 kt) & 3, then the paired tile on the next two
@@ -1895,6 +1958,8 @@ hipError_t launch_gemm_pb(int epi, const GemmArgsB& g_in, hipStream_t st) {
     // the packed epilogue (k_gemm_pb, "PACKABLE"): only where every output of the half step is a byte plane of the 0/1 sample
     g.packed_epi = (g.packed_epi && epi == EPI_HALFSTEP && g.noise == NOISE_BERNOULLI && g.act == ACT_SIGMOID && g.a_bytes && !g.rp &&
                     g.out && g.out_bytes && g.outT && g.outT_f8 && !g.side && !g.out_f32) ? 1 : 0;
+    // the skipped k-step of the last tile (k_gemm_pb, one_tile "TAIL"): the three-piece byte-plane walk of a half step only
+    g.k_tail = (g.k_tail && epi == EPI_HALFSTEP && g.a_bytes && g.pb_max == 3 && g.nseg == 1 && g.nsplit == 1) ? 1 : 0;
     const int nblk = g.grid_m * g.grid_n * g.nsplit;
     {   // XCD blocks: the factorisation 8 = xz * xr * xc (xz | nsplit, xr | grid_m, xc | grid_n) with the fewest operand rows
         // per XCD, weighted by the tiles a k-tile loads (one A tile per segment, npb B tiles)
