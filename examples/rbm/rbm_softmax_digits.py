@@ -24,6 +24,12 @@ An optional top-level key `"fine_tune"` (absent by default: nothing changes) add
 end to end on log p(y | v) by `DBN.fine_tune` -- e.g. `{"top_hidden": 128, "top_hps": {"lr": 0.001, "epochs": 5, "batch_size": 128},
 "epochs": 10, "lr": 0.0005, "momentum": 0.5, "weight_decay": 0.0}`.  Its held-out accuracy is printed before and after
 fine-tuning.  README.md, "Fine-tuning a DBN".
+
+An optional top-level key `"joint_model"` (absent by default: nothing changes) trains a label RBM (`n_labels = 10`, Bernoulli
+visibles) generatively on `[pixels | one-hot label]` and uses it as the generative model it is: the mean `log p(v, y)` and
+`log p(v)` of the held-out digits under an AIS estimate of log Z (`label="free"`), and a few joint samples `(v, y)` from Gibbs
+chains whose label block is free -- e.g. `{"hidden": 128, "hps": {"lr": 0.001, "epochs": 10, "batch_size": 128}, "n_chains": 256,
+"betas": 1000, "n_samples": 5, "burn_in": 500}`.  README.md, "Free label blocks".
 """
 import json
 import os
@@ -161,6 +167,26 @@ def fine_tune_demo(mc, ft):
     return acc0, acc1
 
 
+def joint_model_demo(mc, jm):
+    """The opt-in "joint_model" key: log p(v, y) and joint samples of a generatively trained label RBM (label="free")."""
+    V, y = mc._load_training_data()
+    Vt, yt = mc._load_test_data()
+    rbm = RBM(jm.get("hps", mc.conf["rbm_hps"]), int(jm.get("hidden", 128)), name="joint", mode=0, n_labels=10, seed=int(jm.get("seed", 11)))
+    print("Train a label RBM on [pixels | one-hot label].")
+    rbm.fit(V, y=y, verbose=0)
+    log_z = rbm.log_partition(n_chains=int(jm.get("n_chains", 256)), betas=int(jm.get("betas", 1000)), base_rates=rbm.join(V, y),
+                              label="free")
+    print("log Z = %.3f +- %.3f (AIS, %d chains)" % (log_z, rbm.last_ais["stderr"], rbm.last_ais["n_chains"]))
+    if yt is not None:
+        print("held-out mean log p(v, y) = %.3f, mean log p(v) = %.3f"
+              % (rbm.log_likelihood(Vt, y=yt, log_z=log_z, label="free"), rbm.log_likelihood(Vt, log_z=log_z, label="free")))
+    n = int(jm.get("n_samples", 5))
+    S = rbm.sample(n, burn_in=int(jm.get("burn_in", 500)), label="free")
+    for row in S:
+        print("sampled class %d with %d of %d pixels on" % (int(row[-10:].argmax()), int(row[:-10].sum()), row.size - 10))
+    return log_z
+
+
 def main():
     with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "rbm_softmax_conf.json")) as f:
         conf = json.load(f)
@@ -173,6 +199,8 @@ def main():
         mc.test()
     if conf.get("fine_tune"):
         fine_tune_demo(mc, conf["fine_tune"])
+    if conf.get("joint_model"):
+        joint_model_demo(mc, conf["joint_model"])
     print("Elapsed time: {0:f}s".format(time.time() - ts))
 
 

@@ -612,7 +612,8 @@ int kurbm_gibbs_run(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t 
  *     rewritten by the label site (so a persistent chain keeps one-hot blocks), and for the last v_t the label columns of the
  *     visible-bias sums become sum_rows(v_batch - v_neg) over the new block; h_neg, the statistics and the apply see that v_neg.
  *     The positive phase and the v -> h half steps need nothing: a one-hot block is 0/1 columns.
- * The x3 / bf16 / one-launch paths have no label site: a label RBM trains on the fp32 five-launch path.
+ * The x3 / bf16 / one-launch TRAINING paths have no label site: a label RBM trains on the fp32 five-launch path.  The Gibbs and AIS
+ * runs have one: "free label blocks" below.
  * KURBM_ERR_ARG, before anything is enqueued, for n_labels outside [2, 64] or >= n_vis, a mode other than Bernoulli, and whatever
  * the plain twin refuses; KURBM_ERR_WORKSPACE for a short workspace.
  *
@@ -731,6 +732,55 @@ int kurbm_backprop_layer(kurbm_ctx* ctx, const kurbm_params* p, int act, const f
 int kurbm_disc_backprop(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* v_batch, int rows, int ldv,
                         float* delta_out, float* e_in /* nullable */, int ldei, float* nll_mean /* nullable */, void* ws,
                         size_t ws_bytes, kurbm_stream_t stream);
+
+/*
+ * Free label blocks: the softmax site inside the Gibbs and AIS runs, so that a label RBM is the generative model it was trained as --
+ * joint samples (v, y), a sampled class for given pixels, and log Z of p(v, y).  n_pix = n_vis - C; the block is the last C columns;
+ * Bernoulli visibles only.  The label site is the one stated under "softmax label units".
+ *
+ * Gibbs sweep t with a free block (kurbm_gibbs_run_labels; everything else as kurbm_gibbs_run):
+ *     h_t as there: the one-hot block of v_{t-1} is ordinary 0/1 columns.  The pixels of v_t as there.
+ *     The block of v_t is then ONE draw of softmax(x), x_c = b_v[n_pix + c] + sum_j h_t,j W[n_pix + c][j]: subtract the max, exp, sum in
+ *     class order, divide; the drawn class is the first c with u < p_0 + ... + p_c on a running fp32 sum, else C-1;
+ *     u = u(chain0 + chain, col n_pix) at (KURBM_STREAM_GIBBS_V, step t): one uniform per row.
+ *     After the block is drawn, clamped pixels are copied back as there.
+ *     On a kept sweep the block of v_out is the one-hot vector and the block of prob_out is p.
+ *   W is read as the fp32 master rows, not the mirror; h is read from the run's hidden plane (bytes or one bf16 piece: exactly 0 / 1),
+ *   and the block is written into the current visible plane in its format.  One small launch per sweep, in front of the clamp launch.
+ *   Every sum runs in a fixed order and nothing is atomic: the same call twice gives identical bits.
+ *   `mode` must be KURBM_MODE_VISIBLE_BERNOULLI.  The label columns of `clamp` are NOT read: the block is free here, and a clamped
+ *   block is kurbm_gibbs_run's business.  The workspace is that of kurbm_gibbs_workspace_bytes.
+ *
+ * AIS with a label block (kurbm_ais_run_labels; everything else as kurbm_ais_run), over v = [pixels | one-hot], a = v.W + b_h on
+ * all n_vis columns:
+ *     p*_beta(v) = exp((1 - beta) b_A.v + beta b_v.v) prod_j (1 + exp(beta a_j(v)))
+ *     log Z_0 = n_hid ln 2 + sum_{i < n_pix} softplus(b_A,i) + logsumexp_c b_A[n_pix + c]
+ *     start:  pixels [u < sigmoid(b_A)]; the class from softmax(b_A[n_pix:]) by the site's recipe, u = u(row, n_pix) at
+ *             (KURBM_STREAM_AIS_INIT, 0)
+ *     k:      Delta_k = dbeta (sum_{i < n_pix} (b_v - b_A)_i v_i + (b_v - b_A)[n_pix + y]) + sum_j [softplus(beta_k a_j) - softplus(beta_{k-1} a_j)]
+ *             h and the pixels as there; the block is one draw of softmax(x),
+ *             x_c = (1 - beta_k) b_A[n_pix + c] + beta_k (b_v[n_pix + c] + sum_j h_j W[n_pix + c][j]), u = u(row, n_pix) at (KURBM_STREAM_AIS_V, k).
+ *   One temperature is the two GEMM launches of kurbm_ais_run -- the h -> v one on the n_pix pixel rows of W -- the label site on the
+ *   fp32 hidden plane, and the accumulate launch.  The site's row partial needs one group row more than kurbm_ais_workspace_bytes
+ *   holds at some shapes (n_pix = 33, C = 2): the size query is kurbm_ais_labels_workspace_bytes (0 for a bad shape).
+ * kurbm_ais_step_labels: the test hook, teacher-forced like kurbm_ais_step; v_in [n_chains][ldv] carries a one-hot block (its class is
+ *   the first unit above 1/2).  Additional nullable planes prob_y [n_chains][ldp] (the block's p) and u_y [n_chains].  The label
+ *   columns of prob_v / u_v are not written.
+ * KURBM_ERR_ARG, before anything is enqueued and with nothing written: n_labels outside [2, 64] or >= n_vis, a mode other than
+ * Bernoulli, and whatever the plain twin refuses; KURBM_ERR_WORKSPACE for short buffers.
+ */
+int kurbm_gibbs_run_labels(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, void* mirror, size_t mirror_bytes, const float* v_init,
+                           int v_pieces, int ldv, int n_chains, uint64_t chain0, uint64_t seed, int mode, int burn_in, int thin,
+                           int n_keep, const uint8_t* clamp, float* v_out, float* prob_out, int ldo, size_t keep_stride, void* ws,
+                           size_t ws_bytes, kurbm_stream_t stream);
+size_t kurbm_ais_labels_workspace_bytes(kurbm_ctx* ctx, int n_chains, int n_vis, int n_hid, int n_labels);
+int kurbm_ais_run_labels(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* base_bias, const double* betas, int n_betas,
+                         int n_chains, uint64_t chain0, uint64_t seed, double* logw, float* v_final, int ldv, void* ws, size_t ws_bytes,
+                         kurbm_stream_t stream);
+int kurbm_ais_step_labels(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* base_bias, double beta_prev, double beta,
+                          int k, const float* v_in, int ldv, int n_chains, uint64_t chain0, uint64_t seed, float* dlogw, float* h,
+                          int ldh, float* v_out, int ldvo, float* prob_h, float* u_h, float* prob_v, float* u_v, float* prob_y, int ldp,
+                          float* u_y, void* ws, size_t ws_bytes, kurbm_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -124,6 +124,14 @@ SIGNATURES = {
     "kurbm_gibbs_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
     "kurbm_gibbs_run": (_i, [_vp, _PP, _vp, _sz, _vp, _i, _i, _i, C.c_uint64, C.c_uint64, _i, _i, _i, _i, _vp, _vp, _vp, _i, _sz,
                              _vp, _sz, _vp]),
+    # free label blocks: the plain twins' arguments with n_labels behind the parameters; the step hook adds prob_y, ldp, u_y
+    "kurbm_gibbs_run_labels": (_i, [_vp, _PP, _i, _vp, _sz, _vp, _i, _i, _i, C.c_uint64, C.c_uint64, _i, _i, _i, _i, _vp, _vp, _vp, _i,
+                                    _sz, _vp, _sz, _vp]),
+    "kurbm_ais_labels_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
+    "kurbm_ais_run_labels": (_i, [_vp, _PP, _i, _vp, C.POINTER(C.c_double), _i, _i, C.c_uint64, C.c_uint64, _vp, _vp, _i, _vp, _sz,
+                                  _vp]),
+    "kurbm_ais_step_labels": (_i, [_vp, _PP, _i, _vp, C.c_double, C.c_double, _i, _vp, _i, _i, C.c_uint64, C.c_uint64, _vp, _vp, _i,
+                                   _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     # softmax label units: n_labels follows the parameters; mom is nullable
     "kurbm_label_sample": (_i, [_vp, _PP, _i, _vp, _i, _i, _RP, _vp, _i, _vp, _i, _vp, _vp]),
     "kurbm_cd_step_labels": (_i, [_vp, _PP, _i, _vp, _i, _i, _OP, _i, _vp, _sz, _vp, _MP]),

@@ -572,10 +572,15 @@ static int backprop_input(kurbm_ctx* ctx, const kurbm_params* p, int n_in, const
 // One temperature: v -> h launch (h and the softplus-difference partials), the accumulate step (it reads the (b_v - b_A).v
 // partials the PREVIOUS temperature -- or the start -- left in vpart, so it runs before they are rewritten), h -> v launch
 // (v and its partials).  ng_v_in: groups of vpart that hold the partials of v_in.
+// ls (kurbm_ais_run_labels): the last ls->C visible units are a label block -- the h -> v launch then covers the pixel columns alone
+// (they are W's top rows, and the epilogue masks the columns from N on inside a group of 16), and the label site behind it draws the
+// block of v_out and leaves the block's (b_v - b_A) term as the group row behind the pixels' (w.ng_v - 1).
+struct AisLabels { int C; float* prob_y; int ldp; float* u_y; };
 static int ais_temperature(kurbm_ctx* ctx, const kurbm_params* p, const float* base_bias, double beta_prev, double beta, int k,
                            const float* v_in, int ldv, int rows, uint64_t chain0, uint64_t seed, const AisWorkspace& w, int ng_v_in,
                            double* logw, float* dlogw, float* h, int ldh, float* v_out, int ldvo, float* prob_h, float* u_h,
-                           float* prob_v, float* u_v, hipStream_t st) {
+                           float* prob_v, float* u_v, hipStream_t st, const AisLabels* ls = nullptr) {
+    const int n_pix = p->n_vis - (ls ? ls->C : 0);
     AisGemmArgs g;
     memset(static_cast<void*>(&g), 0, sizeof g);
     g.B0 = p->W; g.ldb = p->ldw;
@@ -589,7 +594,7 @@ static int ais_temperature(kurbm_ctx* ctx, const kurbm_params* p, const float* b
     for (int layout = LAYOUT_VH; layout <= LAYOUT_HV; ++layout) {
         const bool vh = layout == LAYOUT_VH;
         g.A0 = vh ? v_in : h; g.lda = vh ? ldv : ldh;
-        g.K = vh ? p->n_vis : p->n_hid; g.N = vh ? p->n_hid : p->n_vis;
+        g.K = vh ? p->n_vis : p->n_hid; g.N = vh ? p->n_hid : n_pix;
         g.nkt = g.K / 32; g.kt_total = g.nkt; g.kt_per_split = g.nkt;
         const int cfg = pick_cfg(ctx->plan.ncu, rows, g.N, &g.grid_m, &g.grid_n, force_cfg(&ctx->plan, layout));
         g.m_fastest = (g.grid_m < g.grid_n) ? 1 : 0;
@@ -599,17 +604,40 @@ static int ais_temperature(kurbm_ctx* ctx, const kurbm_params* p, const float* b
         g.rng = make_rng(seed, chain0, vh ? KURBM_STREAM_AIS_H : KURBM_STREAM_AIS_V, (uint32_t)k);
         HIP_TRY(launch_gemm_ais(layout, cfg, g, st));
         if (vh) HIP_TRY(launch_ais_accumulate(w.sppart, w.ng_h, w.vpart, ng_v_in, w.ld_part, g.dbeta, logw, dlogw, rows, st));
+        if (!vh && ls) {
+            LabelSiteArgs a;
+            memset(static_cast<void*>(&a), 0, sizeof a);
+            a.h = h; a.ldh = ldh; a.hfmt = LS_H_F32;
+            a.W = p->W; a.ldw = p->ldw; a.b_v = p->b_v;
+            a.base_bias = base_bias; a.beta = g.beta; a.one_minus_beta = g.one_minus_beta;
+            a.v = v_out; a.ldv = ldvo;
+            a.prob = ls->prob_y; a.ldp = ls->ldp; a.prob_col0 = 0; a.out_u = ls->u_y;
+            a.part = w.vpart + (size_t)(w.ng_v - 1) * w.ld_part;
+            a.rows = rows; a.n_pix = n_pix; a.C = ls->C; a.n_hid = p->n_hid;
+            a.rng = g.rng;
+            HIP_TRY(launch_label_site(a, st));
+        }
     }
     return KURBM_OK;
 }
 
 static int check_ais_common(kurbm_ctx* ctx, const kurbm_params* p, const float* base_bias, int n_chains, const void* ws,
-                            size_t ws_bytes) {
+                            size_t ws_bytes, int n_labels = 0, bool with_labels = false) {
     if (!ctx) return fail_msg(KURBM_ERR_ARG, "ctx is null");
     if (int e = check_params(p)) return e;
+    if (with_labels)
+        if (int e = check_labels(p, n_labels)) return e;
     if (!base_bias) return fail_msg(KURBM_ERR_ARG, "base_bias is null");
     if (n_chains <= 0) return fail_msg(KURBM_ERR_ARG, "n_chains must be positive");
-    return check_workspace(ws, carve_ais(nullptr, n_chains, p->n_vis, p->n_hid).bytes, ws_bytes);
+    return check_workspace(ws, carve_ais(nullptr, n_chains, p->n_vis, p->n_hid, n_labels).bytes, ws_bytes);
+}
+
+static int check_betas(const double* betas, int n_betas) {
+    if (!betas || n_betas < 2) return fail_msg(KURBM_ERR_ARG, "betas: null, or fewer than two temperatures");
+    if (betas[0] != 0.0 || betas[n_betas - 1] != 1.0) return fail_msg(KURBM_ERR_ARG, "betas must run from 0 to 1");
+    for (int k = 1; k < n_betas; ++k)
+        if (!(betas[k] > betas[k - 1])) return fail_msg(KURBM_ERR_ARG, "betas must be strictly increasing (betas[%d])", k);
+    return KURBM_OK;
 }
 
 // the operands of kurbm_outer_delta / kurbm_outer_partial and their workspace
@@ -811,6 +839,57 @@ int kurbm_ais_step(kurbm_ctx* ctx, const kurbm_params* p, const float* base_bias
                              make_rng(seed, chain0, KURBM_STREAM_AIS_INIT, 0), st));
     return ais_temperature(ctx, p, base_bias, beta_prev, beta, k, v_in, ldv, n_chains, chain0, seed, w, 1, nullptr, dlogw, h, ldh,
                            v_out, ldvo, prob_h, u_h, prob_v, u_v, st);
+}
+
+// ---- AIS with a label block (include/kurbm.h, "free label blocks") ----------------------
+size_t kurbm_ais_labels_workspace_bytes(kurbm_ctx* ctx, int n_chains, int n_vis, int n_hid, int n_labels) {
+    if (!ctx || n_chains <= 0 || n_vis <= 0 || n_hid <= 0 || n_labels < 2 || n_labels > 64 || n_labels >= n_vis) return 0;
+    return carve_ais(nullptr, n_chains, n_vis, n_hid, n_labels).bytes;
+}
+
+int kurbm_ais_run_labels(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* base_bias, const double* betas, int n_betas,
+                         int n_chains, uint64_t chain0, uint64_t seed, double* logw, float* v_final, int ldv, void* ws, size_t ws_bytes,
+                         kurbm_stream_t stream) {
+    if (int e = check_ais_common(ctx, p, base_bias, n_chains, ws, ws_bytes, n_labels, true)) return e;
+    if (int e = check_betas(betas, n_betas)) return e;
+    if (!logw || (reinterpret_cast<uintptr_t>(logw) & 7u)) return fail_msg(KURBM_ERR_ARG, "logw is null or misaligned");
+    if (v_final && bad_matrix(v_final, ldv, p->n_vis)) return fail_msg(KURBM_ERR_ARG, "v_final: misaligned, ld %% 4 != 0 or ld < n_vis");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const AisWorkspace w = carve_ais(ws, n_chains, p->n_vis, p->n_hid, n_labels);
+    HIP_TRY(launch_ais_start_labels(w.v, w.ldv, p->b_v, base_bias, w.vpart, logw, n_chains, p->n_vis - n_labels, n_labels, 1,
+                                    make_rng(seed, chain0, KURBM_STREAM_AIS_INIT, 0), st));
+    const AisLabels ls = {n_labels, nullptr, 0, nullptr};
+    for (int k = 1; k < n_betas; ++k) {
+        const bool last = k == n_betas - 1 && v_final;
+        if (int e = ais_temperature(ctx, p, base_bias, betas[k - 1], betas[k], k, w.v, w.ldv, n_chains, chain0, seed, w,
+                                    k == 1 ? 1 : w.ng_v, logw, nullptr, w.h, w.ldh, last ? v_final : w.v, last ? ldv : w.ldv,
+                                    nullptr, nullptr, nullptr, nullptr, st, &ls))
+            return e;
+    }
+    return KURBM_OK;
+}
+
+int kurbm_ais_step_labels(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, const float* base_bias, double beta_prev, double beta,
+                          int k, const float* v_in, int ldv, int n_chains, uint64_t chain0, uint64_t seed, float* dlogw, float* h,
+                          int ldh, float* v_out, int ldvo, float* prob_h, float* u_h, float* prob_v, float* u_v, float* prob_y, int ldp,
+                          float* u_y, void* ws, size_t ws_bytes, kurbm_stream_t stream) {
+    if (int e = check_ais_common(ctx, p, base_bias, n_chains, ws, ws_bytes, n_labels, true)) return e;
+    if (!(beta_prev >= 0.0 && beta > beta_prev && beta <= 1.0)) return fail_msg(KURBM_ERR_ARG, "need 0 <= beta_prev < beta <= 1");
+    if (k < 1) return fail_msg(KURBM_ERR_ARG, "k must be >= 1");
+    if (!dlogw) return fail_msg(KURBM_ERR_ARG, "dlogw is null");
+    if (int e = check_batch(v_in, n_chains, ldv, p->n_vis, "v_in")) return e;
+    if (int e = check_batch(h, n_chains, ldh, p->n_hid, "h")) return e;
+    if (int e = check_batch(v_out, n_chains, ldvo, p->n_vis, "v_out")) return e;
+    if ((prob_h && !aligned16(prob_h)) || (u_h && !aligned16(u_h)) || (prob_v && !aligned16(prob_v)) || (u_v && !aligned16(u_v)))
+        return fail_msg(KURBM_ERR_ARG, "a test plane is misaligned");
+    if (prob_y && ldp < n_labels) return fail_msg(KURBM_ERR_ARG, "prob_y: ldp < n_labels");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const AisWorkspace w = carve_ais(ws, n_chains, p->n_vis, p->n_hid, n_labels);
+    HIP_TRY(launch_ais_start_labels(const_cast<float*>(v_in), ldv, p->b_v, base_bias, w.vpart, nullptr, n_chains, p->n_vis - n_labels,
+                                    n_labels, 0, make_rng(seed, chain0, KURBM_STREAM_AIS_INIT, 0), st));
+    const AisLabels ls = {n_labels, prob_y, ldp, u_y};
+    return ais_temperature(ctx, p, base_bias, beta_prev, beta, k, v_in, ldv, n_chains, chain0, seed, w, 1, nullptr, dlogw, h, ldh,
+                           v_out, ldvo, prob_h, u_h, prob_v, u_v, st, &ls);
 }
 
 int kurbm_outer_delta(kurbm_ctx* ctx, const float* v_pos, const float* h_pos, const float* v_neg, const float* h_neg,

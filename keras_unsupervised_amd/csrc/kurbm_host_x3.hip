@@ -485,13 +485,20 @@ size_t kurbm_gibbs_workspace_bytes(kurbm_ctx* ctx, int n_chains, int n_vis, int 
     return carve_gibbs(&ctx->plan, nullptr, n_chains, n_vis, n_hid, v_pieces, mode, false).bytes;
 }
 
-int kurbm_gibbs_run(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t mirror_bytes, const float* v_init, int v_pieces,
-                    int ldv, int n_chains, uint64_t chain0, uint64_t seed, int mode, int burn_in, int thin, int n_keep,
-                    const uint8_t* clamp, float* v_out, float* prob_out, int ldo, size_t keep_stride, void* ws, size_t ws_bytes,
-                    kurbm_stream_t stream) {
+// n_labels > 0: the last n_labels visible units are a FREE label block (kurbm_gibbs_run_labels): the label site rewrites the block of
+// every v_t behind the h -> v launch, and the label columns of `clamp` are not read (the mask is made of the pixels alone)
+static int gibbs_run_any(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, void* mirror, size_t mirror_bytes, const float* v_init,
+                         int v_pieces, int ldv, int n_chains, uint64_t chain0, uint64_t seed, int mode, int burn_in, int thin, int n_keep,
+                         const uint8_t* clamp, float* v_out, float* prob_out, int ldo, size_t keep_stride, void* ws, size_t ws_bytes,
+                         kurbm_stream_t stream) {
     // every check before the first launch: a refused call has written nothing
     if (!ctx) return fail_msg(KURBM_ERR_ARG, "ctx is null");
     if (int e = check_params(p)) return e;
+    if (n_labels) {
+        if (int e = check_labels(p, n_labels)) return e;
+        if (mode != KURBM_MODE_VISIBLE_BERNOULLI) return fail_msg(KURBM_ERR_ARG, "a label RBM has Bernoulli visibles");
+    }
+    const int n_pix = p->n_vis - n_labels;
     if (n_chains <= 0) return fail_msg(KURBM_ERR_ARG, "n_chains must be positive");
     if (int e = check_mode(mode)) return e;
     if (int e = check_v_pieces(v_pieces)) return e;
@@ -515,7 +522,7 @@ int kurbm_gibbs_run(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t 
     // the start plane, converted once; with a mask, the current plane starts as its copy (same format) so that every sweep reads vc
     HIP_TRY(launch_f32_to_bf16(v_init, n_chains, p->n_vis, ldv, w.v0, w.Lv, w.Kb, nullptr, 0, 0, w.sp, w.planeV, 0, nullptr, 0, st,
                                0, w.sbytes ? 1 : 0));
-    if (clamp) HIP_TRY(launch_gibbs_mask(clamp, p->n_vis, w.maskp, w.Kv, w.cbytes ? 1 : 0, st));
+    if (clamp) HIP_TRY(launch_gibbs_mask(clamp, n_pix, w.maskp, w.Kv, w.cbytes ? 1 : 0, st));
     int e;
     for (long long t = 1; t <= T; ++t) {
         const bool first = t == 1;
@@ -537,6 +544,18 @@ int kurbm_gibbs_run(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t 
             if (kept) { ho.out_f32 = v_out + joff; ho.prob_f32 = prob_out ? prob_out + joff : nullptr; ho.ldo32 = ldo; }
             if ((e = half_step_b(ctx, LAYOUT_HV, p, m, w.hb, w.Lh, 1, 0, n_chains, act_v, noise_v, &r, ho, st, w.hbytes))) return e;
         }
+        if (n_labels) {   // the block of v_t: one draw of softmax(b_v + h_t.W^T), in the plane's format (and the fp32 planes of a kept sweep)
+            LabelSiteArgs a;
+            memset(static_cast<void*>(&a), 0, sizeof a);
+            a.h = w.hb; a.ldh = w.Lh; a.hfmt = w.hbytes ? LS_H_BYTES : LS_H_BF16;
+            a.W = p->W; a.ldw = p->ldw; a.b_v = p->b_v;
+            if (w.cbytes) { a.vb = reinterpret_cast<unsigned char*>(w.vc); a.ldvb = (size_t)w.Lv; }
+            else { a.vp = w.vc; a.ldvp = w.Lv; a.pieces = w.cp; a.plane = w.planeV; }
+            if (kept) { a.v = v_out + joff; a.ldv = ldo; a.prob = prob_out ? prob_out + joff : nullptr; a.ldp = ldo; a.prob_col0 = n_pix; }
+            a.rows = n_chains; a.n_pix = n_pix; a.C = n_labels; a.n_hid = p->n_hid;
+            a.rng = r;
+            HIP_TRY(launch_label_site(a, st));
+        }
         if (clamp) {   // v_t[:, c] = v_init[:, c]: the plane the next sweep reads and, on a kept sweep, the fp32 planes just written
             GibbsClampArgs a;
             memset(static_cast<void*>(&a), 0, sizeof a);
@@ -549,6 +568,25 @@ int kurbm_gibbs_run(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t 
         }
     }
     return KURBM_OK;
+}
+
+int kurbm_gibbs_run(kurbm_ctx* ctx, const kurbm_params* p, void* mirror, size_t mirror_bytes, const float* v_init, int v_pieces,
+                    int ldv, int n_chains, uint64_t chain0, uint64_t seed, int mode, int burn_in, int thin, int n_keep,
+                    const uint8_t* clamp, float* v_out, float* prob_out, int ldo, size_t keep_stride, void* ws, size_t ws_bytes,
+                    kurbm_stream_t stream) {
+    return gibbs_run_any(ctx, p, 0, mirror, mirror_bytes, v_init, v_pieces, ldv, n_chains, chain0, seed, mode, burn_in, thin, n_keep,
+                         clamp, v_out, prob_out, ldo, keep_stride, ws, ws_bytes, stream);
+}
+
+int kurbm_gibbs_run_labels(kurbm_ctx* ctx, const kurbm_params* p, int n_labels, void* mirror, size_t mirror_bytes, const float* v_init,
+                           int v_pieces, int ldv, int n_chains, uint64_t chain0, uint64_t seed, int mode, int burn_in, int thin,
+                           int n_keep, const uint8_t* clamp, float* v_out, float* prob_out, int ldo, size_t keep_stride, void* ws,
+                           size_t ws_bytes, kurbm_stream_t stream) {
+    if (!ctx) return fail_msg(KURBM_ERR_ARG, "ctx is null");
+    if (int e = check_params(p)) return e;
+    if (int e = check_labels(p, n_labels)) return e;     // (n_labels = 0 is the plain run's, not a label run)
+    return gibbs_run_any(ctx, p, n_labels, mirror, mirror_bytes, v_init, v_pieces, ldv, n_chains, chain0, seed, mode, burn_in, thin,
+                         n_keep, clamp, v_out, prob_out, ldo, keep_stride, ws, ws_bytes, stream);
 }
 
 // ---- mirrors, workspaces, half steps, steps ----------------------------------------------------------------------------------

@@ -128,6 +128,36 @@ struct ClassLogitArgs {
 hipError_t launch_label_sample(const LabelArgs& a, hipStream_t st);
 hipError_t launch_class_logits(const ClassLogitArgs& a, hipStream_t st);
 
+// kurbm_labelsite.hip: the label site inside the Gibbs and AIS runs (include/kurbm.h, "free label blocks")
+//   launch_label_site: one 16-row band per wave and workgroup.  h [rows][ldh] in format hfmt (ldh in ELEMENTS of that format: floats,
+//                      bytes of the k-permuted byte plane, bf16 values of one piece); x_c = b_v[n_pix + c] + sum_j h_j W[n_pix + c][j],
+//                      and with base_bias (AIS) x_c <- one_minus_beta * base_bias[n_pix + c] + beta * x_c; p = softmax(x), one draw
+//                      with the uniform of (rng.row0 + row, col = n_pix) at `rng` (row0: any value).  The block is written to every
+//                      plane that is given: vb (byte plane, ldvb bytes per row, k-permuted positions, 0x40 = one), vp (`pieces`
+//                      bf16 planes `plane` elements apart, ldvp elements per row: hi = 1.0 / 0, the others 0), v (fp32, columns
+//                      n_pix ..); prob[row][prob_col0 + c] = p_c; out_u[row] = u; part[row] = (b_v - base_bias)[n_pix + class].
+//   launch_ais_start_labels: launch_ais_start for [pixels | one-hot]: pixels as there, the class from softmax(base_bias[n_pix:]) with
+//                      u(row, n_pix) (draw = 1) or read from v (draw = 0); vpart[row] = (b_v - b_A).v[row], ONE group of partials.
+enum { LS_H_F32 = 0, LS_H_BYTES = 1, LS_H_BF16 = 2 };
+struct LabelSiteArgs {
+    const void* h; int ldh, hfmt;
+    const float* W; int ldw;       // the WHOLE weight matrix; the label rows start at row n_pix
+    const float* b_v;
+    const float* base_bias;        // nullable: no temperature in x
+    float beta, one_minus_beta;
+    unsigned char* vb; size_t ldvb;
+    uint16_t* vp; int ldvp, pieces; size_t plane;
+    float* v; int ldv;
+    float* prob; int ldp, prob_col0;
+    float* out_u;
+    float* part;
+    int rows, n_pix, C, n_hid;
+    RngArgs rng;
+};
+hipError_t launch_label_site(const LabelSiteArgs& a, hipStream_t st);
+hipError_t launch_ais_start_labels(float* v, int ldv, const float* b_v, const float* base_bias, float* vpart, double* logw, int rows,
+                                   int n_pix, int C, int draw, const RngArgs& rng, hipStream_t st);
+
 // kurbm_classgrad.hip: the discriminative gradient of a label RBM (include/kurbm.h, "discriminative and hybrid training")
 //   launch_class_grad:  from a [rows][lda] (the pre-activation plane), logits / prob [rows][ldl] (launch_class_logits) and the one-hot
 //                       block of v [rows][ldv]: the plane g = S_y - H_bar [rows][ldg], S_y and H_bar themselves [rows][ldh] (nullable), nll [rows], and per tile of CG_ROWS rows the partial

@@ -304,13 +304,15 @@ struct AisWorkspace {
     int ldv, ldh, ld_part, ng_h, ng_v;
     size_t bytes;
 };
-inline AisWorkspace carve_ais(void* base, int rows, int n_vis, int n_hid) {
+// n_labels > 0 (kurbm_ais_run_labels): the h -> v launch covers the n_pix = n_vis - n_labels pixel columns and the label site adds ONE
+// group row behind their ceil(n_pix / 16) -- which can be one more than ceil(n_vis / 16) (n_pix = 33, C = 2).
+inline AisWorkspace carve_ais(void* base, int rows, int n_vis, int n_hid, int n_labels = 0) {
     AisWorkspace w;
     w.ldv = round_up(n_vis, 4);
     w.ldh = round_up(n_hid, 4);
     w.ld_part = round_up(rows, 4);
     w.ng_h = ceil_div(n_hid, 16);
-    w.ng_v = ceil_div(n_vis, 16);
+    w.ng_v = n_labels > 0 ? ceil_div(n_vis - n_labels, 16) + 1 : ceil_div(n_vis, 16);
     Arena ar(base);
     w.v = ar.take<float>((size_t)rows * w.ldv);
     w.h = ar.take<float>((size_t)rows * w.ldh);

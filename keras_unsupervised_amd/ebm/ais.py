@@ -39,16 +39,38 @@ def check_schedule(betas):
     return b
 
 
-def base_rate_bias(V, smoothing=0.05):
+def base_rate_bias(V, smoothing=0.05, n_labels=0):
     """Visible bias b_A of the base-rate model (W = 0) of data V [rows, n_vis]: the logit of the column means, smoothed
-    towards 1/2 -- p = (1 - smoothing) mean + smoothing / 2 -- so that an all-zero or all-one column stays finite."""
+    towards 1/2 -- p = (1 - smoothing) mean + smoothing / 2 -- so that an all-zero or all-one column stays finite.
+    n_labels = C > 0: the last C columns are a one-hot label block, a softmax unit whose base model is categorical -- its
+    entries are log((1 - smoothing) freq_c + smoothing / C), the log of the smoothed class frequencies."""
     if not 0.0 < smoothing <= 1.0:
         raise ValueError("smoothing must be in (0, 1]")
     V = np.asarray(V, dtype=np.float64)
     if V.ndim != 2 or V.shape[0] == 0:
         raise ValueError("expected a non-empty [rows, n_vis] matrix")
-    p = (1.0 - smoothing) * np.clip(V.mean(axis=0), 0.0, 1.0) + 0.5 * smoothing
-    return np.log(p) - np.log1p(-p)
+    n_labels = _check_labels(n_labels, V.shape[1])
+    mean = np.clip(V.mean(axis=0), 0.0, 1.0)
+    p = (1.0 - smoothing) * mean + 0.5 * smoothing
+    b = np.log(p) - np.log1p(-p)
+    if n_labels:
+        b[-n_labels:] = np.log((1.0 - smoothing) * mean[-n_labels:] + smoothing / n_labels)
+    return b
+
+
+def _check_labels(n_labels, n_vis):
+    n_labels = int(n_labels)
+    if n_labels and not (2 <= n_labels <= 64 and n_labels < n_vis):
+        raise ValueError("n_labels must be 0 or in [2, 64] and below n_vis = %d, got %d" % (n_vis, n_labels))
+    return n_labels
+
+
+def _logsumexp(x, axis=None):
+    x = np.asarray(x, dtype=np.float64)
+    m = np.max(x, axis=axis, keepdims=True)
+    m = np.where(np.isfinite(m), m, 0.0)
+    out = np.log(np.sum(np.exp(x - m), axis=axis, keepdims=True)) + m
+    return out.reshape(()) if axis is None else np.squeeze(out, axis=axis)
 
 
 def log_mean_exp(x):
@@ -60,42 +82,79 @@ def log_mean_exp(x):
     return float(m + np.log(np.mean(np.exp(x - m))))
 
 
-def log_z0(base_bias, n_hid):
-    """log Z of the base-rate model: n_hid ln 2 + sum_i softplus(b_A,i)."""
-    return float(n_hid * np.log(2.0) + np.sum(np.logaddexp(0.0, np.asarray(base_bias, dtype=np.float64))))
+def log_z0(base_bias, n_hid, n_labels=0):
+    """log Z of the base-rate model: n_hid ln 2 + sum_i softplus(b_A,i); with a label block of n_labels = C units (the last
+    C entries) n_hid ln 2 + sum_{i < n_pix} softplus(b_A,i) + logsumexp_c b_A[n_pix + c]."""
+    b = np.asarray(base_bias, dtype=np.float64).reshape(-1)
+    n_labels = _check_labels(n_labels, b.size)
+    n_pix = b.size - n_labels
+    z = n_hid * np.log(2.0) + np.sum(np.logaddexp(0.0, b[:n_pix]))
+    if n_labels:
+        z += _logsumexp(b[n_pix:])
+    return float(z)
 
 
-def estimate(logw, base_bias, n_hid):
+def estimate(logw, base_bias, n_hid, n_labels=0):
     """(log Z estimate, its standard error, log Z_0) from the chains' log weights.  The standard error is the delta method's:
-    std(w) / (mean(w) sqrt(M)) on w = exp(logw - max)."""
+    std(w) / (mean(w) sqrt(M)) on w = exp(logw - max).  n_labels: as log_z0."""
     logw = np.asarray(logw, dtype=np.float64).reshape(-1)
-    z0 = log_z0(base_bias, n_hid)
+    z0 = log_z0(base_bias, n_hid, n_labels)
     w = np.exp(logw - np.max(logw))
     stderr = float(np.std(w) / (np.mean(w) * np.sqrt(w.size)))
     return z0 + log_mean_exp(logw), stderr, z0
 
 
-def exact_log_partition(W, b_h, b_v):
+def exact_log_partition(W, b_h, b_v, n_labels=0):
     """Exact log Z = log sum_v exp(-F(v)) by enumerating the states of the SMALLER layer (the other one sums in closed form).
-    ValueError when min(n_vis, n_hid) > 24."""
+    ValueError when min(n_vis, n_hid) > 24.
+    n_labels = C > 0: the last C visible units are a one-hot label block, Z = sum over (pixels, class, h).  Enumerating the
+    hidden side sums the block in closed form (logsumexp_c (b_v + W h)[n_pix + c] beside the pixels' softplus terms);
+    enumerating the visible side runs over pixels x classes.  The smaller of n_hid and n_pix is enumerated."""
     W = np.asarray(W, dtype=np.float64)
     b_h = np.asarray(b_h, dtype=np.float64).reshape(-1)
     b_v = np.asarray(b_v, dtype=np.float64).reshape(-1)
     if W.shape != (b_v.size, b_h.size):
         raise ValueError("W has shape %s, expected %s" % (W.shape, (b_v.size, b_h.size)))
+    n_labels = _check_labels(n_labels, b_v.size)
+    if n_labels:
+        return _exact_log_partition_labels(W, b_h, b_v, n_labels)
     if W.shape[1] < W.shape[0]:          # enumerate the hiddens: the same sum with the roles swapped
         W, b_h, b_v = W.T, b_v, b_h
     n = W.shape[0]
     if n > 24:
         raise ValueError("exact_log_partition enumerates 2^min(n_vis, n_hid) states: %d units is too many (at most 24)" % n)
     total = -np.inf
+    for S in _states(n):
+        e = S @ b_v + np.logaddexp(0.0, S @ W + b_h).sum(axis=1)
+        total = np.logaddexp(total, _logsumexp(e))
+    return float(total)
+
+
+def _states(n):
+    """Every 0/1 vector of n units, in blocks of 2^14 rows (float64)."""
     bits = np.arange(n, dtype=np.int64)
     for lo in range(0, 1 << n, 1 << 14):
         idx = np.arange(lo, min(lo + (1 << 14), 1 << n), dtype=np.int64)
-        S = ((idx[:, None] >> bits[None, :]) & 1).astype(np.float64)
-        e = S @ b_v + np.logaddexp(0.0, S @ W + b_h).sum(axis=1)
-        m = e.max()
-        total = np.logaddexp(total, m + np.log(np.exp(e - m).sum()))
+        yield ((idx[:, None] >> bits[None, :]) & 1).astype(np.float64)
+
+
+def _exact_log_partition_labels(W, b_h, b_v, C):
+    n_pix, n_hid = b_v.size - C, b_h.size
+    n = min(n_pix, n_hid)
+    if n > 24:
+        raise ValueError("exact_log_partition enumerates 2^min(n_pix, n_hid) states: %d units is too many (at most 24)" % n)
+    total = -np.inf
+    if n_hid <= n_pix:       # hidden states: pixels and the block sum in closed form
+        for H in _states(n_hid):
+            x = H @ W.T + b_v
+            e = H @ b_h + np.logaddexp(0.0, x[:, :n_pix]).sum(axis=1) + _logsumexp(x[:, n_pix:], axis=1)
+            total = np.logaddexp(total, _logsumexp(e))
+    else:                    # pixel states x classes: the hiddens sum in closed form
+        for S in _states(n_pix):
+            a = S @ W[:n_pix] + b_h
+            for c in range(C):
+                e = S @ b_v[:n_pix] + b_v[n_pix + c] + np.logaddexp(0.0, a + W[n_pix + c]).sum(axis=1)
+                total = np.logaddexp(total, _logsumexp(e))
     return float(total)
 
 

@@ -239,15 +239,20 @@ class DBN(object):
             V_p = rbm_layer.hidden_probs(V_p)
         return layers[0]._ret(V_p, kind, False)
 
-    def sample(self, n_samples, burn_in=1000, thin=100, n_chains=None, init=None, return_prob=False, seed=None, label=None):
+    def sample(self, n_samples, burn_in=1000, thin=100, n_chains=None, init=None, return_prob=False, seed=None, label=None,
+               return_labels=False):
         """n_samples "dreams" of the network (extension), [n_samples, n_vis of the first layer]: a Gibbs run in the TOP RBM
         (RBM.sample: burn_in, thin, n_chains, seed as there), then one ancestral pass down through inv_transform of the lower
         layers, in the order of DBN.inv_transform.  init [n_chains, n_vis of the first layer] starts the top chains from its
         sampled representation (layer.transform up to the top RBM's input).  return_prob: the bottom layer's visible_probs of the
         last hidden states instead of its sample.  A host array, or where init came from.
         label (a label RBM on top): the class, or one per chain, whose one-hot block the top chains start from and keep; only the
-        pixel part of the top RBM's states goes down."""
+        pixel part of the top RBM's states goes down.  label='free': the top chains sample the block too (RBM.sample).
+        return_labels (a label RBM on top): additionally the class of each sample's top state, integers [n_samples] -- the sampled
+        class with label='free', the given one otherwise -- as (samples, labels)."""
         layers = self._layers()
+        if return_labels and not self._top_labels():
+            raise ValueError("return_labels needs a label RBM on top")
         if not all(layer.built for layer in layers):
             raise ValueError("sample needs built RBM layers")
         kind, top_init = "numpy", None
@@ -257,6 +262,14 @@ class DBN(object):
                 top_init = rbm_layer.transform(top_init)
         n_samples = int(n_samples)
         H_p, _, _ = layers[-1]._sample(n_samples, n_chains, burn_in, thin, top_init, None, False, seed, label)
+        classes = None
+        if return_labels:
+            classes = H_p.view()[:n_samples, H_p.cols - self._top_labels():].argmax(dim=1)
+            classes = classes.cpu().numpy() if kind == "numpy" else (classes if kind == "device" else classes.to(kind))
+        if classes is not None:
+            done = lambda out: (out, classes)
+        else:
+            done = lambda out: out
         if self._top_labels() and len(layers) > 1:     # the label block stays up there: the layer below sees the pixel columns
             H_p = DeviceMatrix(H_p.t, H_p.rows, H_p.cols - self._top_labels(), H_p.ld)
         if H_p.rows != n_samples:                 # (kept, chain) order: the first n_samples rows
@@ -264,8 +277,8 @@ class DBN(object):
         if len(layers) == 1:
             if return_prob:
                 raise ValueError("return_prob needs a layer below the top RBM (use RBM.sample(return_prob=True))")
-            return layers[0]._ret(H_p, kind, False)
+            return done(layers[0]._ret(H_p, kind, False))
         for rbm_layer in reversed(layers[1:-1]):
             H_p = rbm_layer.inv_transform(H_p)
         H_p = layers[0].visible_probs(H_p) if return_prob else layers[0].inv_transform(H_p)
-        return layers[0]._ret(H_p, kind, False)
+        return done(layers[0]._ret(H_p, kind, False))

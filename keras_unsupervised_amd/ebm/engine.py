@@ -700,10 +700,13 @@ class DeviceRBM:
         return F
 
     # -- annealed importance sampling (include/kurbm.h: kurbm_ais_run) --------------------------
-    def ais_workspace(self, n_chains):
-        n = int(self.lib.kurbm_ais_workspace_bytes(self.ctx.handle, int(n_chains), self.n_vis, self.n_hid))
+    def ais_workspace(self, n_chains, n_labels=0):
+        if n_labels:
+            n = int(self.lib.kurbm_ais_labels_workspace_bytes(self.ctx.handle, int(n_chains), self.n_vis, self.n_hid, int(n_labels)))
+        else:
+            n = int(self.lib.kurbm_ais_workspace_bytes(self.ctx.handle, int(n_chains), self.n_vis, self.n_hid))
         if n == 0:
-            raise _lib.KurbmError("kurbm_ais_workspace_bytes failed")
+            raise _lib.KurbmError("kurbm_ais%s_workspace_bytes failed" % ("_labels" if n_labels else ""))
         return self._alloc_bytes(n, "ais_workspace", zero=False)
 
     def _base_bias(self, base_bias):
@@ -719,22 +722,50 @@ class DeviceRBM:
         t.copy_(torch.from_numpy(b))
         return t
 
-    def ais_run(self, betas, n_chains, base_bias=None, chain0=0, seed=0, want_v=False, ws=None):
+    def ais_run(self, betas, n_chains, base_bias=None, chain0=0, seed=0, want_v=False, ws=None, n_labels=0):
         """log w of n_chains AIS chains (global indices chain0 ...) over the schedule `betas` (host float64, 0 .. 1, strictly
         increasing) in ONE library call: two GEMM launches and one small launch per temperature, nothing read back here.
-        Returns (logw: float64 device tensor [n_chains], v_final: DeviceMatrix or None)."""
+        n_labels > 0: the last n_labels visible units are a softmax label block (kurbm_ais_run_labels: one more small launch per
+        temperature).  Returns (logw: float64 device tensor [n_chains], v_final: DeviceMatrix or None)."""
         betas = np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
-        n_chains = int(n_chains)
+        n_chains, n_labels = int(n_chains), int(n_labels)
         with torch.cuda.device(self.device):
             ba = self._base_bias(base_bias)
-            ws = self.ais_workspace(n_chains) if ws is None else ws
+            ws = self.ais_workspace(n_chains, n_labels) if ws is None else ws
             logw = self._alloc_floats(2 * n_chains, "logw", zero=False).view(torch.float64)
             vf = self._alloc_out(n_chains, self.n_vis, "v_final") if want_v else None
-            check(self.lib.kurbm_ais_run(self.ctx.handle, C.byref(self.params), ba.data_ptr(),
-                                         betas.ctypes.data_as(C.POINTER(C.c_double)), int(betas.size), n_chains, int(chain0),
-                                         int(seed), logw.data_ptr(), vf.ptr() if want_v else None, vf.ld if want_v else 0,
-                                         ws.data_ptr(), ws.numel(), self._stream()))
+            tail = (betas.ctypes.data_as(C.POINTER(C.c_double)), int(betas.size), n_chains, int(chain0), int(seed), logw.data_ptr(),
+                    vf.ptr() if want_v else None, vf.ld if want_v else 0, ws.data_ptr(), ws.numel(), self._stream())
+            if n_labels:
+                check(self.lib.kurbm_ais_run_labels(self.ctx.handle, C.byref(self.params), n_labels, ba.data_ptr(), *tail))
+            else:
+                check(self.lib.kurbm_ais_run(self.ctx.handle, C.byref(self.params), ba.data_ptr(), *tail))
         return logw, vf
+
+    def ais_step_labels(self, v, n_labels, beta_prev, beta, k, base_bias=None, chain0=0, seed=0, want_planes=True, ws=None):
+        """Test hook: ais_step for a label RBM (kurbm_ais_step_labels); v carries a one-hot block.  The dict of ais_step plus,
+        with want_planes, prob_y (DeviceMatrix [rows, n_labels]) and u_y (device tensor [rows])."""
+        if v.cols != self.n_vis:
+            raise ValueError("input has %d columns, expected %d" % (v.cols, self.n_vis))
+        rows, n_labels = v.rows, int(n_labels)
+        with torch.cuda.device(self.device):
+            ba = self._base_bias(base_bias)
+            ws = self.ais_workspace(rows, n_labels) if ws is None else ws
+            out = {"dlogw": self._alloc_floats(rows, "dlogw", zero=False)}
+            for key, cols, want in (("h", self.n_hid, True), ("prob_h", self.n_hid, want_planes), ("u_h", self.n_hid, want_planes),
+                                    ("v", self.n_vis, True), ("prob_v", self.n_vis, want_planes), ("u_v", self.n_vis, want_planes),
+                                    ("prob_y", n_labels, want_planes)):
+                out[key] = self._alloc_out(rows, cols, key) if want else None
+            out["u_y"] = self._alloc_floats(rows, "u_y", zero=False) if want_planes else None
+            ptr = lambda key: out[key].ptr() if out[key] is not None else None
+            check(self.lib.kurbm_ais_step_labels(self.ctx.handle, C.byref(self.params), n_labels, ba.data_ptr(), float(beta_prev),
+                                                 float(beta), int(k), v.ptr(), v.ld, rows, int(chain0), int(seed),
+                                                 out["dlogw"].data_ptr(), ptr("h"), out["h"].ld, ptr("v"), out["v"].ld, ptr("prob_h"),
+                                                 ptr("u_h"), ptr("prob_v"), ptr("u_v"), ptr("prob_y"),
+                                                 out["prob_y"].ld if want_planes else 0,
+                                                 out["u_y"].data_ptr() if want_planes else None, ws.data_ptr(), ws.numel(),
+                                                 self._stream()))
+        return out
 
     def ais_step(self, v, beta_prev, beta, k, base_bias=None, chain0=0, seed=0, want_planes=True, ws=None):
         """Test hook: temperature k of such a run on the chains in DeviceMatrix v (kurbm_ais_step, teacher-forced).  Returns a
@@ -777,10 +808,12 @@ class DeviceRBM:
         return t
 
     def gibbs_run(self, v, burn_in=1, thin=1, n_keep=1, chain0=0, seed=0, mode=MODE_VISIBLE_BERNOULLI, clamp=None,
-                  want_prob=False, ws=None):
+                  want_prob=False, ws=None, n_labels=0):
         """Gibbs sweeps from the rows of DeviceMatrix v (one chain per row, global indices chain0 ...) in ONE library call: two
         x3 half-step launches per sweep, the states kept in their operand format, nothing read back here.  Kept sample j is the
         state after burn_in + j * thin sweeps.  clamp: see _clamp_mask; those units keep v's values.
+        n_labels > 0: the last n_labels visible units are a FREE softmax label block, drawn by the label site every sweep
+        (kurbm_gibbs_run_labels: one more small launch per sweep); the block's entries of clamp are not read.
         Returns (samples, probs): DeviceMatrix [n_keep * rows, n_vis] in (kept, chain) order; probs (want_prob, else None) holds
         the activated value each sample was drawn from."""
         if v.cols != self.n_vis:
@@ -795,11 +828,13 @@ class DeviceRBM:
             ws = self.gibbs_workspace(rows, vp, mode) if ws is None else ws
             out = self._alloc_out(max(n_keep, 1) * rows, self.n_vis, "gibbs_v")
             prob = self._alloc_out(max(n_keep, 1) * rows, self.n_vis, "gibbs_prob") if want_prob else None
-            check(self.lib.kurbm_gibbs_run(self.ctx.handle, C.byref(self.params), mir.data_ptr(), mir.numel(), v.ptr(), vp, v.ld,
-                                           rows, int(chain0), int(seed), int(mode), int(burn_in), int(thin), n_keep,
-                                           mask.data_ptr() if mask is not None else None, out.ptr(),
-                                           prob.ptr() if prob is not None else None, out.ld, rows * out.ld,
-                                           ws.data_ptr(), ws.numel(), self._stream()))
+            tail = (mir.data_ptr(), mir.numel(), v.ptr(), vp, v.ld, rows, int(chain0), int(seed), int(mode), int(burn_in), int(thin),
+                    n_keep, mask.data_ptr() if mask is not None else None, out.ptr(), prob.ptr() if prob is not None else None,
+                    out.ld, rows * out.ld, ws.data_ptr(), ws.numel(), self._stream())
+            if n_labels:
+                check(self.lib.kurbm_gibbs_run_labels(self.ctx.handle, C.byref(self.params), int(n_labels), *tail))
+            else:
+                check(self.lib.kurbm_gibbs_run(self.ctx.handle, C.byref(self.params), *tail))
             if mode == MODE_VISIBLE_BERNOULLI and mask is None:
                 out.bf16_exact = out.binary = True        # 0/1: one bf16 piece, no need to look
         return out, prob

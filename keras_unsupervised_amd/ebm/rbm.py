@@ -322,9 +322,14 @@ class RBM(object):
         return (input_shape[0], self.output_dim)          # rbm.py:94-95
 
     # ------------------------------------------------------------------ likelihood -------
-    def _check_likelihood(self, what):
-        if self.n_labels:
-            raise ValueError("%s is not available for a label RBM: the AIS kernels have no softmax site yet" % what)
+    def _check_likelihood(self, what, label=None):
+        if label is not None and label != "free":
+            raise ValueError("label= of %s is None or 'free', got %r" % (what, label))
+        if label is not None and not self.n_labels:
+            raise ValueError("label= needs a label RBM (n_labels > 0)")
+        if self.n_labels and label is None:
+            raise ValueError("%s of a label RBM is that of the joint model p(v, y): pass label='free' (the AIS run then samples "
+                             "the label block at its softmax site)" % what)
         if self.mode != MODE_VISIBLE_BERNOULLI:
             raise ValueError("%s is defined for MODE_VISIBLE_BERNOULLI only: in MODE_VISIBLE_GAUSSIAN the hidden site is a "
                              "thresholded relu (rbm.py:58-59), not the Bernoulli unit of an energy model this estimator is valid for"
@@ -334,7 +339,7 @@ class RBM(object):
         if not self.built:
             raise ValueError("%s needs a built RBM (call build / fit / transform first)" % what)
 
-    def log_partition(self, n_chains=512, betas=1000, base_rates=None, seed=None, method="ais"):
+    def log_partition(self, n_chains=512, betas=1000, base_rates=None, seed=None, method="ais", label=None):
         """log Z of the model (extension; the reference has no likelihood estimate).
 
         method 'ais': annealed importance sampling (Salakhutdinov & Murray 2008) from the base-rate model to this one, n_chains
@@ -344,8 +349,12 @@ class RBM(object):
         model) or a bias vector [n_vis].  seed: of the chains' draws (default: the RBM's).
         method 'exact': enumeration (ais.exact_log_partition; at most 24 units on the smaller side).
         Returns a float and fills self.last_ais = {log_z, stderr, log_z0, logw, n_chains, n_betas}.  The fit / transform counters
-        and the weights are not touched."""
-        self._check_likelihood("log_partition")
+        and the weights are not touched.
+        label='free' (label RBM only, and required there): log Z of the joint model p(v, y) over [pixels | one-hot] -- the AIS
+        chains sample the label block at its softmax site (kurbm_ais_run_labels), the base model of the block is categorical
+        (ais.base_rate_bias(V, n_labels=C)), and 'exact' enumerates pixels x classes or the hidden side."""
+        self._check_likelihood("log_partition", label)
+        C_lab = self.n_labels if label == "free" else 0
         if method not in ("ais", "exact"):
             raise ValueError("method must be 'ais' or 'exact', got %r" % (method,))
         if method == "ais":          # (arguments first: a bad schedule is refused whether or not the RBM is built)
@@ -361,7 +370,7 @@ class RBM(object):
         self._check_built("log_partition")
         if method == "exact":
             W, b_h, b_v = self._dev.get_weights()
-            log_z = ais.exact_log_partition(W, b_h, b_v)
+            log_z = ais.exact_log_partition(W, b_h, b_v, n_labels=C_lab) if C_lab else ais.exact_log_partition(W, b_h, b_v)
             self.last_ais = {"log_z": log_z, "stderr": 0.0, "log_z0": None, "logw": None, "n_chains": 0, "n_betas": 0}
             self._ais_at = self._update_count
             return log_z
@@ -370,21 +379,33 @@ class RBM(object):
             b_a = np.zeros(d.n_vis, np.float64)
         else:
             b_a = np.asarray(base_rates, dtype=np.float64)
-            b_a = ais.base_rate_bias(b_a) if b_a.ndim == 2 else b_a.reshape(-1)
+            b_a = (ais.base_rate_bias(b_a, n_labels=C_lab) if C_lab else ais.base_rate_bias(b_a)) if b_a.ndim == 2 else b_a.reshape(-1)
             if b_a.size != d.n_vis:
                 raise ValueError("base_rates has %d columns, the RBM has %d visible units" % (b_a.size, d.n_vis))
         b_a = b_a.astype(np.float32)          # what the device anneals from; log Z_0 is of exactly these values
-        logw, _ = d.ais_run(betas, n_chains, base_bias=b_a, seed=self.seed if seed is None else int(seed))
+        seed = self.seed if seed is None else int(seed)
+        if C_lab:
+            logw, _ = d.ais_run(betas, n_chains, base_bias=b_a, seed=seed, n_labels=C_lab)
+        else:
+            logw, _ = d.ais_run(betas, n_chains, base_bias=b_a, seed=seed)
         logw = logw.cpu().numpy()
-        log_z, stderr, z0 = ais.estimate(logw, b_a, d.n_hid)
+        log_z, stderr, z0 = ais.estimate(logw, b_a, d.n_hid, n_labels=C_lab) if C_lab else ais.estimate(logw, b_a, d.n_hid)
         self.last_ais = {"log_z": log_z, "stderr": stderr, "log_z0": z0, "logw": logw, "n_chains": n_chains, "n_betas": int(betas.size)}
         self._ais_at = self._update_count
         return log_z
 
-    def log_likelihood(self, V, log_z=None, **ais_kwargs):
+    def log_likelihood(self, V, y=None, log_z=None, label=None, **ais_kwargs):
         """Mean log p(v) = -F(v) - log Z over the rows of V.  log_z: given, else the one log_partition cached (self.last_ais; a
-        fit() since then discards it), else log_partition(**ais_kwargs) is run first.  F(v) is cal_free_energy's device path."""
-        self._check_likelihood("log_likelihood")
+        fit() since then discards it), else log_partition(**ais_kwargs) is run first.  F(v) is cal_free_energy's device path.
+        label='free' (label RBM only, and required there) -- the joint model:
+          V n_pix wide with integer labels y, or n_vis wide with a one-hot block: mean log p(v, y) = -F([v | y]) - log Z;
+          V n_pix wide without y: the mean marginal log p(v) = v.b_v[:n_pix] + logsumexp_c class_logits(v) - log Z.
+        V is validated before any log Z is computed."""
+        self._check_likelihood("log_likelihood", label)
+        if y is not None and label != "free":
+            raise ValueError("y= needs a label RBM and label='free'")
+        if label == "free":
+            return self._log_likelihood_labels(V, y, log_z, ais_kwargs)
         if log_z is None:
             cached = self.last_ais is not None and self._ais_at == self._update_count and not ais_kwargs
             log_z = self.last_ais["log_z"] if cached else self.log_partition(**ais_kwargs)
@@ -396,6 +417,40 @@ class RBM(object):
             raise ValueError("log_likelihood of an empty matrix")
         F = self._dev.free_energy(x, x.rows, compute="x3" if self._large(x.rows) else None)
         return float(-F.double().mean().item() - float(log_z))
+
+    def _block_classes(self, x, what):
+        """The classes of the one-hot label blocks of DeviceMatrix x [rows, n_vis] (a device int64 tensor), or ValueError."""
+        blk = x.view()[:, self._n_pix():]
+        if not bool((((blk == 0) | (blk == 1)).all(dim=1) & (blk.sum(dim=1) == 1)).all().item()):
+            raise ValueError("%s: the label block of a label RBM must be one-hot (exactly one of its %d units at 1, the others 0)"
+                             % (what, self.n_labels))
+        return blk.argmax(dim=1)
+
+    def _log_likelihood_labels(self, V, y, log_z, ais_kwargs):
+        self._check_built("log_likelihood")
+        d, n_pix = self._dev, self._n_pix()
+        x, _ = self._as_device(V)
+        if x.cols not in (n_pix, d.n_vis):
+            raise ValueError("V has %d columns, expected %d (pixels) or %d (pixels and labels)" % (x.cols, n_pix, d.n_vis))
+        if x.rows == 0:
+            raise ValueError("log_likelihood of an empty matrix")
+        if x.cols == d.n_vis:
+            if y is not None:
+                raise ValueError("V carries a label block already: pass the pixels alone with y=")
+            self._block_classes(x, "log_likelihood")
+        elif y is not None:
+            x = self._with_label(x, y)
+        if log_z is None:
+            cached = self.last_ais is not None and self._ais_at == self._update_count and not ais_kwargs
+            log_z = self.last_ais["log_z"] if cached else self.log_partition(label="free", **ais_kwargs)
+        if x.cols == d.n_vis:          # joint: the free energy of the joined matrix is -log p*(v, y)
+            F = d.free_energy(x, x.rows)
+            return float(-F.double().mean().item() - float(log_z))
+        logits, _ = d.class_logits(x, self.n_labels, want_prob=False)
+        with device_guard(d.device):
+            lse = torch.logsumexp(logits.view().double(), dim=1)
+            lin = x.view().double() @ d.b_v[:n_pix].double()
+        return float((lin + lse).mean().item() - float(log_z))
 
     # ------------------------------------------------------------------ sampling ---------
     def _take_chains(self, n):
@@ -454,16 +509,40 @@ class RBM(object):
         return out
 
     def _label_clamp(self, clamp, label):
-        """The clamp mask of a Gibbs run on a label RBM: the whole label block (the Gibbs kernels have no softmax site, so a free
-        block would be sampled as independent Bernoulli units) joined with the caller's mask."""
+        """The clamp mask of a Gibbs run on a label RBM, and whether its block is FREE.  Clamped block (label a class, or None with
+        a clamp that covers the block): the whole label block joined with the caller's mask, through kurbm_gibbs_run.
+        label='free': the block is sampled at its softmax site (kurbm_gibbs_run_labels) and the mask holds the caller's pixels; a
+        clamp that covers the WHOLE block is the clamped run again, one that covers part of it is refused."""
         d, n_pix = self._dev, self._n_pix()
         from .engine import clamp_mask
         m = clamp_mask(clamp, d.n_vis) if clamp is not None else np.zeros(d.n_vis, np.uint8)
+        if isinstance(label, str):
+            if label != "free":
+                raise ValueError("label= is a class, one class per chain, or 'free', got %r" % (label,))
+            if not m[n_pix:].any():
+                return (m.astype(bool) if m.any() else None), True
+            if not m[n_pix:].all():
+                raise ValueError("label='free': the clamp covers part of the label block; clamp all of it or none of it")
+            return m.astype(bool), False
         if label is None and not m[n_pix:].all():
-            raise ValueError("a label RBM samples with its label block clamped: pass label= (or a clamp that covers the whole block "
-                             "and an init that carries it)")
+            raise ValueError("a label RBM samples with its label block clamped: pass label= (a class, or label='free' to sample "
+                             "the block at its softmax site), or a clamp that covers the whole block and an init that carries it")
         m[n_pix:] = 1
-        return m.astype(bool)
+        return m.astype(bool), False
+
+    def _free_block_start(self, x, chain0, seed):
+        """A new DeviceMatrix [rows, n_vis]: the pixels of x (n_pix wide) and a one-hot block drawn from softmax(b_v[n_pix:]) with
+        the uniforms u(chain0 + row, n_pix) of site STREAM_GIBBS_V at step 0 -- the label site's rule (first class whose running
+        fp32 sum exceeds u, else the last).  Host tensor arithmetic, as _start_chains."""
+        d, n_pix, C = self._dev, self._n_pix(), self.n_labels
+        with device_guard(d.device):
+            u = d.philox_uniform(x.rows, n_pix + 1, seed, STREAM_GIBBS_V, 0, row0=chain0).view()[:, n_pix]
+            cum = torch.cumsum(torch.softmax(d.b_v[n_pix:].float(), dim=0), dim=0)
+            y = torch.clamp((u.reshape(-1, 1) >= cum.reshape(1, -1)).sum(dim=1), max=C - 1)
+            m = DeviceMatrix.zeros(x.rows, d.n_vis, d.device)
+            m.t[:x.rows, :n_pix].copy_(x.t[:x.rows, :n_pix])
+            m.t[torch.arange(x.rows, device=d.device), n_pix + y] = 1.0
+        return m
 
     def _class_logits(self, V):
         self._check_built("class_logits")
@@ -504,7 +583,10 @@ class RBM(object):
         conditional completion).  return_prob: also the probabilities (Gaussian visibles: the means) the last states were drawn
         from, as (samples, probs).  seed: of the draws (default: the RBM's).  Every call takes fresh chain indices, so two calls
         never reuse draws, and a run is reproducible from (seed, the number of chains handed out before it).  The fit / transform
-        counters, the weights and the cached AIS result are not touched.  Results go back where v came from, as one array."""
+        counters, the weights and the cached AIS result are not touched.  Results go back where v came from, as one array.
+        label (label RBM only): a class, or one per row -- the sweeps keep that one-hot block; or 'free' -- the block is drawn at
+        its softmax site every sweep (kurbm_gibbs_run_labels): v is n_vis wide with a one-hot block, or the pixels alone (the block
+        then starts as sample(init=None) starts it), and clamp may cover pixels: (y, h | clamped pixels)."""
         self._check_built("gibbs")
         n_steps = int(n_steps)
         if n_steps < 1:
@@ -513,19 +595,33 @@ class RBM(object):
         d = self._dev
         if label is not None and not self.n_labels:
             raise ValueError("label= needs a label RBM (n_labels > 0)")
+        free = False
         if self.n_labels:
             # label RBM: the chains start from the one-hot block of `label` (v: pixels, or pixels and a block that is replaced) and
-            # keep it -- class-conditional sweeps through the same kurbm_gibbs_run
-            clamp = self._label_clamp(clamp, label)
-            if label is not None and x.rows > 0:
+            # keep it -- class-conditional sweeps through the same kurbm_gibbs_run; label='free' samples the block
+            clamp, free = self._label_clamp(clamp, label)
+            if label is not None and not isinstance(label, str) and x.rows > 0:
                 x = self._with_label(x, label)
+        seed = self.seed if seed is None else int(seed)
+        if free:
+            if x.cols not in (self._n_pix(), d.n_vis):
+                raise ValueError("v has %d columns, expected %d (pixels) or %d (pixels and labels)" % (x.cols, self._n_pix(), d.n_vis))
+            if x.rows == 0:
+                raise ValueError("gibbs on an empty matrix")
+            if x.cols == d.n_vis:
+                self._block_classes(x, "gibbs(label='free')")
+            chain0 = self._take_chains(x.rows)
+            if x.cols != d.n_vis:        # pixels alone: the block starts as sample(init=None) starts it
+                x = self._free_block_start(x, chain0, seed)
+            out, prob = d.gibbs_run(x, burn_in=n_steps, thin=1, n_keep=1, chain0=chain0, seed=seed, mode=self.mode, clamp=clamp,
+                                    want_prob=bool(return_prob), n_labels=self.n_labels)
+            return self._gibbs_out(out, prob, x.rows, kind, return_prob)
         if x.cols != d.n_vis:
             raise ValueError("v has %d columns, the RBM has %d visible units" % (x.cols, d.n_vis))
         if x.rows == 0:
             raise ValueError("gibbs on an empty matrix")
         out, prob = d.gibbs_run(x, burn_in=n_steps, thin=1, n_keep=1, chain0=self._take_chains(x.rows),
-                                seed=self.seed if seed is None else int(seed), mode=self.mode, clamp=clamp,
-                                want_prob=bool(return_prob))
+                                seed=seed, mode=self.mode, clamp=clamp, want_prob=bool(return_prob))
         return self._gibbs_out(out, prob, x.rows, kind, return_prob)
 
     def _start_chains(self, n_chains, chain0, seed):
@@ -550,7 +646,10 @@ class RBM(object):
         index list, see gibbs) needs init, which carries the clamped values.  return_prob, seed, the chain bookkeeping and what
         is left untouched: as gibbs.  The result is a host array, or goes where init came from.
         label (label RBM only): a class, or one class per chain -- the chains start from that one-hot block and keep it
-        (class-conditional samples); init may then hold the pixels alone.  A label RBM refuses to sample with a free block."""
+        (class-conditional samples); init may then hold the pixels alone.  label='free': joint samples (v, y) -- the block is
+        drawn at its softmax site every sweep (kurbm_gibbs_run_labels); init=None starts it one-hot from softmax(b_v[n_pix:]), an
+        init must carry a one-hot block, and clamp may cover pixels (y, h | clamped pixels).  Without label= a label RBM refuses
+        to sample."""
         out, prob, kind = self._sample(n_samples, n_chains, burn_in, thin, init, clamp, return_prob, seed, label)
         return self._gibbs_out(out, prob, int(n_samples), kind, return_prob)
 
@@ -570,8 +669,11 @@ class RBM(object):
         if label is not None and not self.n_labels:
             raise ValueError("label= needs a label RBM (n_labels > 0)")
         d = self._dev
+        free = False
         if self.n_labels:
-            clamp = self._label_clamp(clamp, label)
+            clamp, free = self._label_clamp(clamp, label)
+            if isinstance(label, str):
+                label = None          # ('free', or a clamp over the whole block with an init that carries it)
             if label is not None:
                 label = self._labels(label, n_chains)
         seed = self.seed if seed is None else int(seed)
@@ -580,16 +682,28 @@ class RBM(object):
             x, kind = self._as_device(init)
             if label is not None and x.rows == n_chains and x.cols == self._n_pix():
                 x = self._with_label(x, label)
-            if x.cols != d.n_vis or x.rows != n_chains:
+            pix_only = free and x.rows == n_chains and x.cols == self._n_pix()     # the block then starts as with init=None
+            if not pix_only and (x.cols != d.n_vis or x.rows != n_chains):
                 raise ValueError("init has shape (%d, %d), expected (%d, %d)" % (x.rows, x.cols, n_chains, d.n_vis))
+            if free and not pix_only:
+                self._block_classes(x, "sample(label='free')")
         chain0 = self._take_chains(n_chains)
+        if init is not None and free and x.cols != d.n_vis:
+            x = self._free_block_start(x, chain0, seed)
         if init is None:
             x = self._start_chains(n_chains, chain0, seed)
+            if free:       # the Bernoulli draws of the block's columns are replaced by ONE categorical draw per chain
+                x = self._free_block_start(DeviceMatrix(x.t, x.rows, self._n_pix(), x.ld), chain0, seed)
+                x.bf16_exact = x.binary = True
         if label is not None:
             x = self._with_label(x, label)      # (a copy: the caller's init is never written)
         n_keep = -(-n_samples // n_chains)
-        out, prob = d.gibbs_run(x, burn_in=burn_in, thin=thin, n_keep=n_keep, chain0=chain0, seed=seed, mode=self.mode,
-                                clamp=clamp, want_prob=bool(return_prob))
+        if free:
+            out, prob = d.gibbs_run(x, burn_in=burn_in, thin=thin, n_keep=n_keep, chain0=chain0, seed=seed, mode=self.mode,
+                                    clamp=clamp, want_prob=bool(return_prob), n_labels=self.n_labels)
+        else:
+            out, prob = d.gibbs_run(x, burn_in=burn_in, thin=thin, n_keep=n_keep, chain0=chain0, seed=seed, mode=self.mode,
+                                    clamp=clamp, want_prob=bool(return_prob))
         return out, prob, kind
 
     def _probs(self, direction, x, act):
